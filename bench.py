@@ -13,7 +13,17 @@ collective on the data path; only the timing uses a MAX all-reduce).
 
 Prints one JSON line (rank 0).  The timed steps replay the forward as one HIP
 graph (engine.GraphedPlan; --no-graph for the eager ctypes launch loop, whose
-~15 us of host time per launch would otherwise bound the step).  Extra fields:
+~15 us of host time per launch would otherwise bound the step).
+
+A plain run does only what the headline figure needs: set-up, --warmup steps, the --steps timed
+steps (ms_per_step = their wall time / --steps), the give-up check of the timed launches, and the
+result line.  --dump-outputs DIR then also writes DIR/output.npy (float32): the output tensor of
+the last timed step as the caller of the forward receives it, (N, 3, H*scale, W*scale) in
+[-1, 1]; above 64 MB a fixed seeded sample of its elements.  Inputs and weights are seeded, so
+two builds run with the same arguments are comparable output for output.
+
+--full adds the legs below, each a run of its own after the timed region (their fields are null
+in a plain run, except model_roofline, which is arithmetic on ms_per_step):
   roofline      — the dominant kernel: the persistent RRDB-trunk kernel
                   (isr_conv_chain: all 240 RDB convs in one launch, ~85 % of the
                   step), against the HBM bound (the trunk's layer-
@@ -92,6 +102,11 @@ def parse():
     ap.add_argument("--lr-size", type=int, default=128)
     ap.add_argument("--blocks", type=int, default=16)
     ap.add_argument("--scale", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: per-kernel roofline, storage A/B, "
+                         "training step, CPU baseline and parity (the options below tune or skip them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/output.npy (float32, at most 64 MB)")
     ap.add_argument("--cpu-tiles", type=int, default=16,
                     help="tiles the CPU baseline runs one by one (the first is the warm-up; all of them are the "
                          "parity reference)")
@@ -114,6 +129,36 @@ def parse():
 def log(msg: str) -> None:
     """Progress on stderr (the JSON line stays the only stdout line)."""
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(dirname: str, out: torch.Tensor) -> None:
+    """DIR/output.npy: the float32 output of the last timed step (CPU tensor).  An output above
+    DUMP_MAX_BYTES is reduced to a fixed sample of its flattened elements (ascending indices drawn
+    with DUMP_SAMPLE_SEED: the same elements in every run of the same shape)."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    keep = DUMP_MAX_BYTES // 4
+    if out.numel() > keep:
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randperm(out.numel(), generator=g)[:keep].sort().values
+        out = out.reshape(-1)[idx]
+    np.save(d / "output.npy", out.contiguous().numpy().astype(np.float32, copy=False))
+    log(f"wrote {d / 'output.npy'}: float32 {tuple(out.shape)}")
+
+
+def finish(result: dict, world: int, rank: int):
+    """Print the result line (rank 0) and leave the process group."""
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    return result if rank == 0 else None
 
 
 def load_traffic(round_tag: str) -> dict:
@@ -390,10 +435,53 @@ def main():
 
     ms = elapsed / args.steps * 1e3
     log(f"inference: {ms:.3f} ms per step")
-    out_timed = out.float().cpu()  # the last timed step's output (the parity leg compares it)
+    # the last timed step's output (written by --dump-outputs; the parity leg compares it)
+    out_timed = out.float().cpu() if args.full or args.dump_outputs else None
     plan.verify()  # a persistent-chain give-up in any timed step (sticky count) voids the run: raises
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_timed)
     hr_px = n * (hw * S) * (hw * S)
     mpix_s = world * hr_px * args.steps / elapsed / 1e6
+    chained = (plan.subs[0] if n_streams > 1 else plan).chain is not None
+    model_flops = engine.generator_flops(hw, hw, args.blocks, S // 2) * n
+    f_over_p = model_flops / (MFMA_BF16_PEAK_TFLOPS * 1e12) * 1e3
+    b_over_bw = TILE_BYTES * n * (hw * hw) / (128 * 128) / (HBM_PEAK_GBS * 1e9) * 1e3
+    model_roofline = {"F_over_P_ms": round(f_over_p, 4), "B_over_BW_ms": round(b_over_bw, 4),
+                      "frac": round(max(f_over_p, b_over_bw) / ms, 4),
+                      "mfma_frac": round(f_over_p / ms, 4), "hbm_frac": round(b_over_bw / ms, 4)}
+    result = {
+        "metric": "4x SR megapixels/sec (HR output) + PSNR vs reference CPU path",
+        "value": round(mpix_s, 3),
+        "unit": "MPix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp16" if gw.dtype == torch.float16 else "bf16",
+        "data": f"synthetic: {weights_desc} (no COCO offline)",
+        "config": {"workload": f"ResNet({args.blocks}, 0.2, scaleRate={S}) RRDB inference, "
+                               f"{hw}x{hw}->{hw * S}x{hw * S}",
+                   "global_batch": n * world, "per_gpu_batch": n, "lr_size": hw, "scale": S,
+                   "parallelism": f"dp{world} (independent tile shards)",
+                   "streams_per_gpu": n_streams, "hip_graph": not args.no_graph,
+                   "trunk": "persistent chain kernel" if chained else "one launch per conv",
+                   "storage": ("fp16" if gw.dtype == torch.float16 else "bf16")
+                              + " activations and packed weights, fp32 accumulation"},
+        "full": args.full,
+        "roofline": None,
+        "roofline_kernels": None,
+        "model_roofline": model_roofline,
+        "model_tflops_per_s": round(model_flops / (ms * 1e-3) / 1e12, 2),
+        "cpu_baseline": None,
+        "storage_ab": None,
+        "parity": None,
+        "train": None,
+    }
+    if not args.full:  # the plain run ends here
+        return finish(result, world, rank)
     # Per-kernel roofline, after the timed region.  The production forward's dominant kernel
     # is the persistent trunk kernel (isr_conv_chain, all 240 RDB convs): timed inside whole
     # forwards run back to back (time_in_forward; its isolated replay is reported beside it).  The per-conv kernels (used by the
@@ -404,7 +492,6 @@ def main():
     npx = n * hw * hw
     traffic = load_traffic(args.round)
     kernels = {}
-    chained = (plan.subs[0] if n_streams > 1 else plan).chain is not None
     if chained and n_streams == 1:
         chain_tag = ("chain", 15 * args.blocks)
         c_iso_ms, c_tags = time_family(plan, {chain_tag}, stream, sp)
@@ -471,12 +558,6 @@ def main():
                        "launches_per_step": len(t_tags) * max(1, n_streams),
                        "flops_per_launch": t_flops,
                        "mfma_frac": round(t_flops / (t_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)}
-    model_flops = engine.generator_flops(hw, hw, args.blocks, S // 2) * n
-    f_over_p = model_flops / (MFMA_BF16_PEAK_TFLOPS * 1e12) * 1e3
-    b_over_bw = TILE_BYTES * n * (hw * hw) / (128 * 128) / (HBM_PEAK_GBS * 1e9) * 1e3
-    model_roofline = {"F_over_P_ms": round(f_over_p, 4), "B_over_BW_ms": round(b_over_bw, 4),
-                      "frac": round(max(f_over_p, b_over_bw) / ms, 4),
-                      "mfma_frac": round(f_over_p / ms, 4), "hbm_frac": round(b_over_bw / ms, 4)}
 
     log("per-kernel roofline timings done")
     # The storage trade of round 6 on this box: the same forward with bf16 storage
@@ -509,7 +590,6 @@ def main():
     if train is not None:
         log(f"train leg: {train['ms_per_step']} ms per step")
 
-    result = None
     if rank == 0:
         cpu = None
         parity = None
@@ -535,41 +615,9 @@ def main():
                              f"first {nt} {hw}x{hw}->{hw * S}x{hw * S} tiles, one tile per call: the first call "
                              f"is the warm-up, value = median of the other {nt - 1} ({sum(ts):.1f} s in all)"}
             parity = parity_report(ref_cpu, out_timed[:nt], torch.cat(refs), hr[:nt], weights_desc)
-        result = {
-            "metric": "4x SR megapixels/sec (HR output) + PSNR vs reference CPU path",
-            "value": round(mpix_s, 3),
-            "unit": "MPix/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp16" if gw.dtype == torch.float16 else "bf16",
-            "data": f"synthetic: {weights_desc} (no COCO offline)",
-            "config": {"workload": f"ResNet({args.blocks}, 0.2, scaleRate={S}) RRDB inference, "
-                                   f"{hw}x{hw}->{hw * S}x{hw * S}",
-                       "global_batch": n * world, "per_gpu_batch": n, "lr_size": hw, "scale": S,
-                       "parallelism": f"dp{world} (independent tile shards)",
-                       "streams_per_gpu": n_streams, "hip_graph": not args.no_graph,
-                       "trunk": "persistent chain kernel" if chained else "one launch per conv",
-                       "storage": ("fp16" if gw.dtype == torch.float16 else "bf16")
-                                  + " activations and packed weights, fp32 accumulation"},
-            "roofline": kernels.get("chain", kernels["growth"]),
-            "roofline_kernels": kernels,
-            "model_roofline": model_roofline,
-            "model_tflops_per_s": round(model_flops / (ms * 1e-3) / 1e12, 2),
-            "cpu_baseline": cpu,
-            "storage_ab": storage_ab,
-            "parity": parity,
-            "train": train,
-        }
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    return result
+        result.update({"roofline": kernels.get("chain", kernels["growth"]), "roofline_kernels": kernels,
+                       "cpu_baseline": cpu, "storage_ab": storage_ab, "parity": parity, "train": train})
+    return finish(result, world, rank)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ P=gpurun_out/profiles_$R   # gpurun merges only gpurun_out/ back (<= 64 MiB); co
 T=/tmp/isr_prof_$R         # raw rocprofv3 output stays off gpurun_out/
 mkdir -p $P $T
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T/prof_bench -o bench -- \
-  python3 bench.py --round $R > $P/prof_bench.json 2> $P/prof_bench.err
+  python3 bench.py --full --round $R > $P/prof_bench.json 2> $P/prof_bench.err
 cp $T/prof_bench/bench_kernel_stats.csv $P/${R}_bench_kernel_stats.csv
 # the dominant kernel (the persistent trunk kernel): its launches from the trace
 python3 - "$T/prof_bench/bench_kernel_trace.csv" "$P/${R}_bench_dominant_by_grid.json" <<'EOF2'
@@ -33,7 +33,7 @@ out = [{"kernel": k, "blocks": b, "dispatches": len(v), "avg_us": round(sum(v) /
 json.dump(out, open(sys.argv[2], "w"), indent=1)
 print(json.dumps(out))
 EOF2
-bash tools/profile_pmc.sh $T/pmc_bench bench.py --no-cpu-baseline --no-storage-ab --steps 5 --warmup 2 --train-steps 0 --round $R
+bash tools/profile_pmc.sh $T/pmc_bench bench.py --full --no-cpu-baseline --no-storage-ab --steps 5 --warmup 2 --train-steps 0 --round $R
 python3 tools/pmc_summary.py $T/pmc_bench --json $P/${R}_pmc_summary.json > /dev/null
 python3 - "$R" "$P" <<'EOF'
 import json, sys
@@ -62,7 +62,7 @@ for k, sub in fam.items():
 json.dump(out, open(f"{P}/{R}_pmc_traffic.json", "w"), indent=1)
 EOF
 cp $P/${R}_pmc_traffic.json profiles/ 2>/dev/null || true
-timeout -k 10 600 python3 bench.py --round $R > $P/${R}_bench.json 2> $P/bench_final.err
+timeout -k 10 600 python3 bench.py --full --round $R > $P/${R}_bench.json 2> $P/bench_final.err
 cat $P/${R}_bench.json
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T/prof_train -o train -- \
   python3 tools/bench_train.py --steps 3 --warmup 2 > $P/${R}_train_bench.json 2> $P/prof_train.err

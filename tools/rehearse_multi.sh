@@ -5,5 +5,5 @@
 set -eu
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29513 bench.py --gpus 2 --steps 5 --warmup 2 --backend gloo --no-cpu-baseline \
+  --master-port 29513 bench.py --full --gpus 2 --steps 5 --warmup 2 --backend gloo --no-cpu-baseline \
   --train-steps 3 --train-warmup 1
