@@ -147,6 +147,9 @@ SIGNATURES = {
     "isr_tuning_tail_stamps": (c_int32, [c_void_p]),
     "isr_tuning_chain_knobs": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     "isr_conv3x3_check": (c_int32, [POINTER(IsrConvDesc)]),
+    "isr_conv3x3_wino_packed_bytes": (c_size_t, [c_int32, c_int32]),
+    "isr_pack_conv3x3_wino_f16": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "isr_conv3x3_wino_fwd": (c_int32, [POINTER(IsrConvDesc), c_void_p]),
     "isr_conv_chain_state_words": (c_size_t, [c_int32, c_int32, c_int32]),
     "isr_conv_chain": (c_int32, [POINTER(IsrChainDesc), c_void_p]),
     "isr_conv_chain_variant": (c_int32, [POINTER(IsrChainDesc), c_int32, c_void_p]),

@@ -23,6 +23,9 @@ int trunk_item_stamps_set(void* p);
 size_t conv3x3_packed_bytes(int cout, int cin);
 int conv3x3_pack(const float* w, void* out, int cout, int cin, hipStream_t s);
 int conv3x3_pack_f16(const float* w, void* out, int cout, int cin, hipStream_t s);
+size_t conv3x3_wino_packed_bytes(int cout, int cin);
+int conv3x3_wino_pack(const float* w, void* out, int cout, int cin, hipStream_t s);
+int conv3x3_wino_fwd_dispatch(const isr_conv_desc* d, hipStream_t s);
 int head9x9_fwd_dispatch(const isr_head_desc* d, hipStream_t s);
 int tail9x9_fwd_dispatch(const isr_tail_desc* d, hipStream_t s);
 int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s);
@@ -261,6 +264,34 @@ int isr_conv3x3_fwd(const isr_conv_desc* d, isr_stream_t s) {
 }
 
 int isr_conv3x3_check(const isr_conv_desc* d) { return conv3x3_validate(d); }
+
+size_t isr_conv3x3_wino_packed_bytes(int32_t cout, int32_t cin) {
+    if (cout <= 0 || cin <= 0) return 0;
+    return isr::conv3x3_wino_packed_bytes(cout, cin);
+}
+
+int isr_pack_conv3x3_wino_f16(const float* w, void* packed, int32_t cout, int32_t cin, isr_stream_t s) {
+    if (!w || !packed) return fail(ISR_ERR_BAD_DESC, "pack_conv3x3_wino_f16: null pointer");
+    if (cin <= 0 || cin % 16)
+        return fail(ISR_ERR_UNSUPPORTED, "pack_conv3x3_wino_f16: cin %d must be a positive multiple of 16", cin);
+    if (cout <= 0 || cout % 32)
+        return fail(ISR_ERR_UNSUPPORTED, "pack_conv3x3_wino_f16: cout %d must be a positive multiple of 32", cout);
+    return launched(isr::conv3x3_wino_pack(w, packed, cout, cin, (hipStream_t)s), "pack_conv3x3_wino_f16");
+}
+
+// The Winograd form's own restrictions first (each names its field), then the direct form's
+// descriptor rules; nothing touches the GPU before both pass.
+int isr_conv3x3_wino_fwd(const isr_conv_desc* d, isr_stream_t s) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "conv3x3_wino: null descriptor");
+    if (d->f16 != 1) return fail(ISR_ERR_UNSUPPORTED, "conv3x3_wino: f16 must be 1 (fp16 storage only, got %d)", d->f16);
+    if (d->shuffle != 1) return fail(ISR_ERR_UNSUPPORTED, "conv3x3_wino: shuffle must be 1 (plain store, got %d)", d->shuffle);
+    if (d->m.data) return fail(ISR_ERR_UNSUPPORTED, "conv3x3_wino: m (mask epilogue) is not supported");
+    if (d->x_sub2) return fail(ISR_ERR_UNSUPPORTED, "conv3x3_wino: x_sub2 is not supported");
+    if (d->taps) return fail(ISR_ERR_UNSUPPORTED, "conv3x3_wino: taps (tap window) is not supported");
+    int rc = conv3x3_validate(d);
+    if (rc != ISR_OK) return rc;
+    return launched(isr::conv3x3_wino_fwd_dispatch(d, (hipStream_t)s), "conv3x3_wino");
+}
 
 size_t isr_conv_chain_state_words(int32_t n, int32_t ha, int32_t wa) {
     if (n <= 0 || ha <= 0 || wa <= 0 || ha % 16 || wa % 32) return 0;

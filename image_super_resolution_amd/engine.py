@@ -54,6 +54,7 @@ class PackedConv:
     b: torch.Tensor  # fp32 bias
     cin: int
     cout: int
+    ww: torch.Tensor | None = None  # fp16 Winograd F(2,3) pack (ops.pack_conv3x3_wino), RDB convs only
 
 
 @dataclass
@@ -73,9 +74,38 @@ class GeneratorWeights:
         return self.head.w.dtype
 
 
-def _pack3(sd, prefix, device, f16: bool = False) -> PackedConv:
+def _pack3(sd, prefix, device, f16: bool = False, wino: bool = False) -> PackedConv:
     w, b = _fold(sd, prefix, device)
-    return PackedConv(ops.pack_conv3x3(w, f16=f16), b, w.shape[1], w.shape[0])
+    return PackedConv(ops.pack_conv3x3(w, f16=f16), b, w.shape[1], w.shape[0],
+                      ops.pack_conv3x3_wino(w) if wino else None)
+
+
+def wino_mode(wino) -> str | None:
+    """Normalised Winograd option: None (off; also "" / "off"), "final" (the 192→64 final conv of
+    every RDB) or "rdb" (all five convs of every RDB)."""
+    if wino is None or wino in ("", "off"):
+        return None
+    if wino not in ("final", "rdb"):
+        raise ValueError(f"wino must be None, 'final' or 'rdb', got {wino!r}")
+    return wino
+
+
+def _resolve_wino(wino, chain, dtype: torch.dtype):
+    """(wino, chain) of a plan: `wino` None takes WINO_DEFAULT (ISR_WINO); a Winograd plan runs the
+    trunk per conv (chain None → off) in fp16 storage."""
+    wino = wino_mode(WINO_DEFAULT if wino is None else wino)
+    if wino is not None:
+        if chain:
+            raise ValueError("wino: the Winograd convs run per conv; chain=True cannot be combined with it")
+        if dtype != torch.float16:
+            raise ValueError("wino: the Winograd convs are fp16 only (pack_generator(f16=True))")
+        chain = False
+    return wino, chain
+
+
+def _wino_conv(wino: str | None, k: int) -> bool:
+    """Whether conv k (0..3 growth, 4 final) of an RDB runs the Winograd form under `wino`."""
+    return wino == "rdb" or (wino == "final" and k == 4)
 
 
 def count_blocks(sd: dict, prefix: str = "") -> int:
@@ -89,18 +119,25 @@ def count_scalers(sd: dict, prefix: str = "") -> int:
 
 
 def pack_generator(sd: dict, *, enchant: bool, add_rate: float = 0.2, prefix: str = "",
-                   device="cuda", f16: bool = True) -> GeneratorWeights:
+                   device="cuda", f16: bool = True, wino: str | None = None) -> GeneratorWeights:
     """Pack a ResNet/EResNet state_dict (reference key schema, fused or not).
 
     `f16` (default): fp16 weights and activations — the inference path's storage type, 3 more
     mantissa bits than bf16 at the same MFMA rate and bytes (x2 generator vs the fp32 oracle:
-    78.9 dB against 59.7 dB in bf16); f16=False keeps bf16 storage."""
+    78.9 dB against 59.7 dB in bf16); f16=False keeps bf16 storage.
+    `wino` ("final" / "rdb"; None takes ISR_WINO): also pack the Winograd F(2,3) weights of the
+    selected RDB convs (PackedConv.ww), which a plan built with `wino` launches; "rdb" packs
+    serve "final" plans too."""
+    wino = wino_mode(WINO_DEFAULT if wino is None else wino)
+    if wino is not None and not f16:
+        raise ValueError("wino: the Winograd convs are fp16 only (f16=False cannot be combined with it)")
     p = prefix
     w0, b0 = _fold(sd, f"{p}conv0", device)
     head = PackedConv(ops.pack_head9x9(w0, f16=f16), b0, w0.shape[1], w0.shape[0])
     nb = count_blocks(sd, p)
-    rdb = [[[_pack3(sd, f"{p}residual.{i}.net.{r}.{c}", device, f16)
-             for c in ("conv0", "conv1", "conv2", "conv3", "conv")] for r in range(3)] for i in range(nb)]
+    rdb = [[[_pack3(sd, f"{p}residual.{i}.net.{r}.{c}", device, f16, _wino_conv(wino, k))
+             for k, c in enumerate(("conv0", "conv1", "conv2", "conv3", "conv"))] for r in range(3)]
+           for i in range(nb)]
     conv1 = _pack3(sd, f"{p}conv1", device, f16)
     scalers = [_pack3(sd, f"{p}scaler.{s}.net.0", device, f16) for s in range(count_scalers(sd, p))]
     w2, b2 = _fold(sd, f"{p}conv2", device)
@@ -159,10 +196,14 @@ class GeneratorPlan:
 
     def __init__(self, gw: GeneratorWeights, n: int, h: int, w: int, device, x_u8: bool, out_u8: bool,
                  mean, std, variants: dict | None = None, chain: bool | None = None,
-                 chain_acquire: bool | None = None):
+                 chain_acquire: bool | None = None, wino: str | None = None):
         """`variants` (tuning only) maps ("conv3x3", cin, cout) or ("conv3x3", "*", cout)
         to an isr_conv3x3_fwd_variant id; unlisted convs use the production kernel.
-        `chain` (default CHAIN_DEFAULT): the RRDB trunk as one persistent isr_conv_chain launch."""
+        `chain` (default CHAIN_DEFAULT): the RRDB trunk as one persistent isr_conv_chain launch.
+        `wino` ("final" / "rdb", default WINO_DEFAULT): those RDB convs through isr_conv3x3_wino_fwd
+        (needs weights from pack_generator(wino=...)); the trunk then runs per conv."""
+        wino, chain = _resolve_wino(wino, chain, gw.dtype)
+        self.wino = wino
         if chain is None:
             chain = CHAIN_DEFAULT
         if chain_acquire is None:
@@ -178,6 +219,7 @@ class GeneratorPlan:
         X, Y, Z = bufs.dense
         lib = ops._lib.load()
         conv, head, tail = lib.isr_conv3x3_fwd, lib.isr_head9x9_fwd, lib.isr_tail9x9_fwd
+        conv_wino = lib.isr_conv3x3_wino_fwd
         dummy_x = torch.empty((n, 3, h, w), dtype=torch.uint8 if x_u8 else torch.float32, device=device)
         cur_h, cur_w = h * 2 ** len(gw.scalers), w * 2 ** len(gw.scalers)
         self.out_shape = (n, 3, cur_h, cur_w)
@@ -188,8 +230,14 @@ class GeneratorPlan:
         L = [(head, self.head_desc, ("head9x9", 3, 64), None)]
         self._conv_variant = lib.isr_conv3x3_fwd_variant
 
-        def c3(src, pc, dst, **kw):
+        def c3(src, pc, dst, use_wino=False, **kw):
             tag = ("conv3x3", pc.cin, pc.cout)
+            if use_wino:  # same tag (around() timing keeps working), the Winograd entry point and pack
+                if pc.ww is None:
+                    raise ValueError(f"wino={wino!r}: these weights carry no Winograd pack for the "
+                                     f"{pc.cin}->{pc.cout} conv; pack with pack_generator(wino={wino!r})")
+                L.append((conv_wino, ops.conv3x3_desc(src, pc.cin, pc.ww, pc.b, pc.cout, dst, **kw), tag, None))
+                return
             v = (variants or {}).get(tag, (variants or {}).get(("conv3x3", "*", pc.cout)))
             L.append((conv, ops.conv3x3_desc(src, pc.cin, pc.w, pc.b, pc.cout, dst, **kw), tag, v))
 
@@ -198,9 +246,9 @@ class GeneratorPlan:
         for blk in gw.rdb:
             for r, (src, dst) in enumerate(((X, Y), (Y, Z), (Z, X))):
                 for k in range(4):
-                    c3(src, blk[r][k], src, y_coff=blk[r][k].cin, slope=LEAKY_DEFAULT)
+                    c3(src, blk[r][k], src, _wino_conv(wino, k), y_coff=blk[r][k].cin, slope=LEAKY_DEFAULT)
                 extra = dict(r2=X, s2=ar) if r == 2 else {}
-                c3(src, blk[r][4], dst, slope=1.0, r1=src, s1=ar, **extra)
+                c3(src, blk[r][4], dst, _wino_conv(wino, 4), slope=1.0, r1=src, s1=ar, **extra)
         self.chain = None
         if chain and gw.rdb and all(e[3] is None for e in L[trunk0:]):  # variants may only touch other layers
             # the whole RRDB trunk as ONE persistent launch (isr_conv_chain): tile-level
@@ -413,7 +461,9 @@ class SplitGeneratorPlan:
 
     def __init__(self, gw: GeneratorWeights, n: int, h: int, w: int, device, x_u8: bool, out_u8: bool,
                  mean, std, splits: int = 2, stagger_us: float = 0.0, variants: dict | None = None,
-                 chain: bool | None = None):
+                 chain: bool | None = None, wino: str | None = None):
+        wino, chain = _resolve_wino(wino, chain, gw.dtype)
+        self.wino = wino
         if n % splits:
             raise ValueError(f"batch {n} does not split into {splits} equal sub-batches")
         self.m = n // splits
@@ -422,7 +472,7 @@ class SplitGeneratorPlan:
         # streams, and two grids that each fill the device cannot all be resident (waits would
         # give up); the split plan is the per-conv form only
         self.subs = [GeneratorPlan(gw, self.m, h, w, device, x_u8, out_u8, mean, std, variants=variants,
-                                   chain=False) for _ in range(splits)]
+                                   chain=False, wino=wino or "off") for _ in range(splits)]
         self.out_shape = (n,) + self.subs[0].out_shape[1:]
         self.out_dtype = self.subs[0].out_dtype
         self.streams = [torch.cuda.Stream(device) for _ in range(splits)]
@@ -482,6 +532,9 @@ def _sleep_cycles_per_us() -> float:
 # relies on the sc1 (L1-bypassing) activation loads alone (-1.5 % time).
 import os as _os
 CHAIN_DEFAULT = _os.environ.get("ISR_CHAIN", "1") == "1"
+# ISR_WINO = "" (off) | "final" | "rdb": the default of every `wino` option — which RDB convs run
+# the opt-in fp16 Winograd F(2,3) form (isr_conv3x3_wino_fwd); a Winograd plan runs per conv.
+WINO_DEFAULT = wino_mode(_os.environ.get("ISR_WINO", ""))
 # The hand-off reads are sc1 LDS-DMA loads, which bypass L1; an agent-scope acquire only
 # invalidates L1, so it adds nothing to them and costs ~1 ms per forward on the trunk kernel
 # (per-wave fences).  Both modes are bitwise-tested (tests/test_gpu_chain.py).
@@ -533,36 +586,40 @@ class GraphedPlan:
 
 
 def make_plan(gw: GeneratorWeights, n: int, h: int, w: int, device, x_u8: bool, out_u8: bool, mean, std,
-              streams: int | None = None, chain: bool | None = None):
+              streams: int | None = None, chain: bool | None = None, wino: str | None = None):
     """GeneratorPlan, or a SplitGeneratorPlan over `streams` (default DEFAULT_STREAMS, or 1
-    with the chained trunk) HIP streams when the batch divides evenly."""
+    with the chained trunk) HIP streams when the batch divides evenly.  `wino`: see GeneratorPlan."""
+    wino, chain = _resolve_wino(wino, chain, gw.dtype)
     chain = CHAIN_DEFAULT if chain is None else chain
     k = (1 if chain else DEFAULT_STREAMS) if streams is None else streams
     if k > 1 and n >= k and n % k == 0:
-        return SplitGeneratorPlan(gw, n, h, w, device, x_u8, out_u8, mean, std, splits=k, chain=chain)
-    return GeneratorPlan(gw, n, h, w, device, x_u8, out_u8, mean, std, chain=chain)
+        return SplitGeneratorPlan(gw, n, h, w, device, x_u8, out_u8, mean, std, splits=k, chain=chain,
+                                  wino=wino or "off")
+    return GeneratorPlan(gw, n, h, w, device, x_u8, out_u8, mean, std, chain=chain, wino=wino or "off")
 
 
 def get_plan(gw: GeneratorWeights, x: torch.Tensor, out_u8: bool, mean, std, streams: int | None = None,
-             chain: bool | None = None):
+             chain: bool | None = None, wino: str | None = None):
     n, c, h, w = x.shape
     if c != 3:
         raise ValueError(f"generator expects 3 input channels, got {c}")
-    key = (n, h, w, str(x.device), x.dtype == torch.uint8, out_u8, tuple(mean), tuple(std), streams, chain)
+    wino = wino_mode(WINO_DEFAULT if wino is None else wino)
+    key = (n, h, w, str(x.device), x.dtype == torch.uint8, out_u8, tuple(mean), tuple(std), streams, chain, wino)
     plan = gw.buffers.get("plan")
     if plan is None or gw.buffers.get("plan_key") != key:
         gw.buffers["plan"] = None  # free the previous geometry first
-        plan = make_plan(gw, n, h, w, x.device, x.dtype == torch.uint8, out_u8, mean, std, streams, chain)
+        plan = make_plan(gw, n, h, w, x.device, x.dtype == torch.uint8, out_u8, mean, std, streams, chain,
+                         wino=wino or "off")
         gw.buffers["plan"] = plan
         gw.buffers["plan_key"] = key
     return plan
 
 
 def run_generator(gw: GeneratorWeights, x: torch.Tensor, *, out_u8: bool = False,
-                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)) -> torch.Tensor:
+                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), wino: str | None = None) -> torch.Tensor:
     """x: NCHW [n,3,h,w] fp32 (normalised) or uint8 (Normalize fused) on the GPU."""
     x = x.contiguous()
-    plan = get_plan(gw, x, out_u8, mean, std)
+    plan = get_plan(gw, x, out_u8, mean, std, wino=wino)
     out = torch.empty(plan.out_shape, dtype=plan.out_dtype, device=x.device)
     return plan.run(x, out)
 

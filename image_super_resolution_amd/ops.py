@@ -291,6 +291,37 @@ def conv3x3(x: ActBuffer, cin: int, wpack: torch.Tensor, bias: torch.Tensor | No
     launch_conv3x3(conv3x3_desc(x, cin, wpack, bias, cout, y, **kw))
 
 
+def pack_conv3x3_wino(w: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp32 OIHW [cout, cin, 3, 3] device weights → the fp16 Winograd F(2,3) pack of
+    isr_conv3x3_wino_fwd (12 transformed values per (cout, cin), layout in include/isr.h)."""
+    _require_gpu(w, "pack_conv3x3_wino")
+    lib = _lib.load()
+    cout, cin = w.shape[:2]
+    w = w.detach().float().contiguous()
+    n = lib.isr_conv3x3_wino_packed_bytes(cout, cin) // 2
+    if out is None:
+        out = torch.empty(n, dtype=torch.float16, device=w.device)
+    elif out.numel() != n or out.dtype != torch.float16:
+        raise ValueError("pack_conv3x3_wino: bad output buffer")
+    check(lib.isr_pack_conv3x3_wino_f16(w.data_ptr(), out.data_ptr(), cout, cin, _stream()),
+          "isr_pack_conv3x3_wino_f16")
+    return out
+
+
+def launch_conv3x3_wino(d: IsrConvDesc) -> None:
+    check(_lib.load().isr_conv3x3_wino_fwd(ctypes.byref(d), _stream()), "isr_conv3x3_wino_fwd")
+
+
+def conv3x3_wino(x: ActBuffer, cin: int, wpack: torch.Tensor, bias: torch.Tensor | None, cout: int,
+                 y: ActBuffer, **kw) -> None:
+    """conv3x3 by Winograd F(2,3) along x (fp16 storage only; wpack from pack_conv3x3_wino).
+    Same keywords and epilogue as conv3x3; the result is not bit-identical to it."""
+    d = conv3x3_desc(x, cin, wpack, bias, cout, y, **kw)  # raises on mixed storage types
+    if not d.f16:
+        raise TypeError("conv3x3_wino: fp16 storage only, got ['torch.bfloat16'] buffers and weights")
+    launch_conv3x3_wino(d)
+
+
 def head9x9_desc(x: torch.Tensor, wpack: torch.Tensor, bias: torch.Tensor | None, y: ActBuffer, *,
                  slope: float, y2: ActBuffer | None = None, y2_coff: int = 0,
                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),

@@ -381,6 +381,28 @@ int isr_tuning_chain_knobs(int32_t delay_ticks, int32_t delay_shift, int32_t k2,
 /* Validation only: ISR_OK when isr_conv3x3_fwd would accept `d` (nothing launched). */
 int isr_conv3x3_check(const isr_conv_desc* d);
 
+/* The same 3x3 conv + fused epilogue by 1-D Winograd F(2,3) along x (fp16 inference, opt-in):
+ * 4 MFMA products per output pair and kernel row instead of 6.  Per kernel row ky, input
+ * channel c and output pair j (outputs x = 2j, 2j+1; inputs d0..d3 = x[2j-1 .. 2j+2]; taps
+ * g0..g2 = W[co][c][ky][0..2]):
+ *   V0 = d0 - d2   V1 = d1 + d2   V2 = d2 - d1   V3 = d1 - d3     (each rounded once to fp16)
+ *   U0 = g0   U1 = (g0+g1+g2)/2   U2 = (g0-g1+g2)/2   U3 = g2     (fp32 from the fp32 weights,
+ *                                                                  rounded once to fp16 at pack time)
+ *   M_p = sum_{ky,c} U_p * V_p       (fp32 accumulation, one accumulator set per p = 0..3)
+ *   y(2j) = M0 + M1 + M2             y(2j+1) = M1 - M2 - M3       (fp32)
+ * followed by isr_conv3x3_fwd's epilogue in its order (v = act(y + bias); v = v*s1 + r1;
+ * v = v*s2 + r2; store to y and y2, rounded once to fp16; exact zeros outside the valid region).
+ * The result is NOT bit-identical to isr_conv3x3_fwd: the input transform rounds to fp16 and the
+ * products differ.  Same descriptor and views; supported: f16 == 1, shuffle == 1, no mask,
+ * x_sub2 == 0, taps == 0, cin % 16 == 0, cout % 32 == 0; bias, slope, r1 / s1 / r1_cn, r2 / s2
+ * and y2 as in the direct form (r1 is always read in the epilogue); y may be a higher channel
+ * slice of x's buffer (the in-place growth convs).  wpack is from isr_pack_conv3x3_wino_f16:
+ * fp16 [cin/16][ky 3][p 4][cout][hpos 2][8], element U_p of W[n][c16*16 + h*8 + e][ky][0..2]
+ * with h = hpos ^ ((n >> 3) & 1); isr_conv3x3_wino_packed_bytes = cout*cin*12*2 bytes. */
+size_t isr_conv3x3_wino_packed_bytes(int32_t cout, int32_t cin);
+int isr_pack_conv3x3_wino_f16(const float* w_oihw, void* packed, int32_t cout, int32_t cin, isr_stream_t s);
+int isr_conv3x3_wino_fwd(const isr_conv_desc* d, isr_stream_t s);
+
 /* Persistent chain of RDB convs (the RRDB trunk, utils/models.py:245-317) in ONE launch:
  * layer i is layers[i] (device memory), each a descriptor isr_conv3x3_check accepts, of
  * kind kinds[i]: 0 = growth conv (cout 32), 1 = RDB final conv (cin 192, cout 64); all

@@ -84,6 +84,9 @@ def run_video(kw, device) -> None:
 
 def runer(**kw):
     src, result = Path(kw["src"]), Path(kw["save_dir"])
+    if kw.get("wino") is not None:  # the default of every pack / plan below (else ISR_WINO, else off)
+        from image_super_resolution_amd import engine
+        engine.WINO_DEFAULT = engine.wino_mode(kw["wino"])
     if src.suffix.lower() in VID_FORMATS + RAW_FORMATS:
         if not torch.cuda.is_available():
             raise RuntimeError("rs.py runs the HIP generator and needs a GPU")
@@ -142,4 +145,7 @@ if __name__ == "__main__":
     p.add_argument("--std", type=float, nargs=3, default=(0.229, 0.224, 0.225))
     p.add_argument("--video_size", type=str, default=None, help="WxH of a raw rgb24 video input")
     p.add_argument("--fps", type=float, default=None, help="frame rate of a raw rgb24 video input")
+    p.add_argument("--wino", choices=("off", "final", "rdb"), default=None,
+                   help="opt-in fp16 Winograd F(2,3) convs: the RDB final convs or all RDB convs; the trunk then "
+                        "runs per conv (default off, or ISR_WINO)")
     runer(**vars(p.parse_args()))
