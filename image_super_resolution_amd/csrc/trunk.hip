@@ -534,11 +534,81 @@ __device__ __forceinline__ void force_publish(const TrunkCtx<K>& c, Stream<K>& s
     st.pend_t = -1;
 }
 
+// The tile after (L, t) in workgroup b's stream of a G-workgroup grid: the next tile of the same
+// layer, else the workgroup's first tile of the next layer; false at the end of the stream.
+__device__ __forceinline__ bool next_item(int L, int t, int b, int G, int ntiles, int nl, int& nL, int& nt) {
+    nL = L;
+    nt = t;
+    if (t + G < ntiles) {
+        nt = t + G;
+        return true;
+    }
+    if (L + 1 < nl) {
+        nL = L + 1;
+        nt = b;
+        return true;
+    }
+    return false;
+}
+
+// Does tile t2's 3x3 neighbourhood contain tile t?
+template <class C>
+__device__ __forceinline__ bool tiles_adjacent(const C& c, int t, int t2) {
+    const int bx = t % c.nbx, tq = t / c.nbx, by = tq % c.nby, im = tq / c.nby;
+    const int bx2 = t2 % c.nbx, nq = t2 / c.nbx, by2 = nq % c.nby, im2 = nq / c.nby;
+    return im == im2 && abs(bx - bx2) <= 1 && abs(by - by2) <= 1;
+}
+
+// The production ring (2 slots, 2 fragment sets, block-issued refill) runs the forward layers'
+// tiles with the chunk stream specialised by role; every other form (deeper rings, one fragment
+// set, the interleaved refill, the masked kind-2 layers) keeps the general chunk, CR_GENERAL.
+template <class K>
+constexpr bool kChunkRoles = K::NST == 2 && K::NSET == 2 && !kTrunkInterleave;
+
+enum : int {
+    CR_GENERAL,  // every test at run time
+    CR_FIRST,    // chunk 0: bias, counted vmcnt wait, staged at its own top when the previous tile could not
+    CR_SECOND,   // chunk 1: the previous tile's publish can still be pending; run-time neighbourhood test
+    CR_STEADY,   // refill = this tile's next chunk, no test at all
+    CR_DEP,      // a steady chunk whose refill may be the first to stage what the previous layer wrote
+    CR_LOOP,     // CR_DEP or, for the tile's last chunk, CR_LAST: chosen at run time
+    CR_LAST      // refill = chunk 0 of the next item (layer kind, self-dependency, bias slot at run time)
+};
+
+// One (layer, tile).  With the chunk roles (kChunkRoles, forward layers) a steady chunk carries no
+// run-time generality:
+//  * its wait is the immediate vmcnt(0): its DMA was issued inside the previous chunk and the wave
+//    has issued no vector-memory instruction since (only a tile's chunk 0 has the previous tile's
+//    epilogue stores / r2 loads behind its DMA, and keeps a counted wait);
+//  * on the 32-cout layers the ring slot is a template argument (the steady run is unrolled by two,
+//    one chunk peeled when it starts on slot 1 or its count is odd), so every LDS offset is a
+//    constant (the 64-cout layers: see FULL below);
+//  * the refill is this tile's next chunk, issued straight-line: the weight-piece count comes from
+//    NF, the halo plane base advances by one add-with-carry per chunk (no 64-bit multiply), the
+//    mark of the staged item is just `issued`;
+//  * the pending publish is tested at chunks 0 and 1 only (chunk 1's DMA is younger than the
+//    previous tile's stores, so its top publishes whatever chunk 0's could not; every forced path
+//    publishes);
+//  * the neighbourhood wait runs at most once per tile, at the chunk whose refill first stages what
+//    the previous layer wrote: the steady run is split there.
+// The last chunk stages the next item's chunk 0, and only there is that item's source computed.
+// Both forms keep the same stream state and hand-off protocol, so their tiles follow each other in
+// one stream, and the same MFMA, fold and epilogue order: the outputs are bit-identical.  The prep
+// kernel guarantees nch >= 4.
 template <class K, int NF, bool MASKED = false, bool H = false>
-__device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, const_rec& rec, int L, int t,
-                                         const Next& nx) {
+__device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, const_rec* recs, int L, int t,
+                                         int nxL, int nxt, bool nx_exists) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int R = K::R, NST = K::NST, CT = 32 * NF, TN = 3, NA = R + 2;
+    constexpr bool ROLES = kChunkRoles<K> && !MASKED;
+    // The 64-cout layers (128 accumulator + 96 fragment VGPRs) keep one chunk body per fold position
+    // plus one loop body (CR_LOOP: run-time slot, run-time boundary / last test): with alternative
+    // chunk bodies in the arms of a branch, or the steady run split into several loops, hipcc moves
+    // the accumulators between register ranges at the joins and spills 700-1,000 VGPRs to scratch
+    // (DESIGN.md section 5).  The 32-cout layers take the full form: compile-time slots, split run.
+    constexpr bool FULL = ROLES && NF == 1;
+    constexpr int WPC = NF == 2 ? tk::WPF : tk::WPG;  // weight pieces per chunk of a forward layer
+    const_rec& rec = recs[L];
     const int wave = wave_id(), lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
     const int bx = t % c.nbx, tmp = t / c.nbx, by = tmp % c.nby, img = tmp / c.nby;
     const int x0 = bx * tk::TW, y0 = by * K::TH;
@@ -549,6 +619,22 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
     const bool has_r2 = NF == 2 && rec.r2 != 0;
     constexpr bool masked = NF == 1 && MASKED;  // kind 2 (gather conv): LeakyReLU' mask from rec.r2
     const Src me = src_of(c, rec, t);
+    // general form: the next item's source up front (the roles compute it in the last chunk)
+    Next nx;
+    if constexpr (!ROLES) {
+        const_rec& nrec = recs[nxL];
+        nx.exists = nx_exists;
+        nx.L = nxL;
+        nx.t = nxt;
+        nx.src = src_of(c, nrec, nxt);
+        nx.first_new = rec_first_new(nrec);
+        nx.nch = rec_nch(nrec);
+        nx.self_dep = tiles_adjacent(c, t, nxt);
+    }
+    // roles: the plane of the next chunk to stage (advanced by pstride per chunk) and that chunk's
+    // offset in the weight table
+    const char* xn = me.x;
+    uint32_t wo = 0;
     bool dep_ok = first_new == tk::NEED_NONE || st.dep_next;
     st.dep_next = false;
     const int bslot = st.tseq & 3;
@@ -571,18 +657,85 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
         trunk_stamp(L, t, c.ntiles, 5);
     };
 
+    // roles: this tile's next chunk into ring slot S — the wave's share of the halo and weight
+    // pieces, every piece count a constant except the ragged last round's
+    auto stage_own = [&](const int sl) {
+        char* dst = smem + sl * K::SLOT;
+        uint32_t n = 0;
+        const auto rx = rsrc_n(xn, c.pstride);
+        if (!(c.abl & 1)) {
+#pragma unroll
+            for (int k = 0; k < K::HPW; ++k) {
+                const int j = wave + K::WM * k;
+                if (K::WM * k + K::WM <= K::HP || j < K::HP) {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ISR_LDS_PTR(dst + j * 1024), 16, c.hoff[k], me.h0, 0,
+                                                             K::HALO_AUX);
+                    ++n;
+                }
+            }
+        }
+        if (!(c.abl & 8)) {
+            const auto rw = rsrc_n(me.w, me.wbytes);
+#pragma unroll
+            for (int k = 0; k < (WPC + K::WM - 1) / K::WM; ++k) {
+                const int j = wave + K::WM * k;
+                if (K::WM * k + K::WM <= WPC || j < WPC) {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(dst + (K::HP + j) * 1024), 16, lane * 16,
+                                                             wo + j * 1024, 0, 0);
+                    ++n;
+                }
+            }
+        }
+        xn += c.pstride;
+        wo += WPC * 1024;
+        return n;
+    };
+
     f32x16 acc[R][NF];
 
     // one K-chunk; FC = the chunk index (0..3) when the residual fold adds its MFMAs to it, else -1
     // (peeled so that the fold's target accumulator is compile-time: a run-time choice made hipcc
     // MFMA into a temporary and copy 16 VGPRs back)
     const uint32_t idv = rec_idv(rec);
-    auto do_chunk = [&](const int ch, auto fc_tag) {
-        constexpr int FC = decltype(fc_tag)::value;
-            const int slot = st.item % NST;
+    // S = the ring slot (roles; -1: st.item % NST at run time), ROLE = the chunk's role
+    auto do_chunk = [&](const int ch, auto fc_tag, auto s_tag, auto role_tag) {
+        constexpr int FC = decltype(fc_tag)::value, S = decltype(s_tag)::value, ROLE = decltype(role_tag)::value;
+        static_assert((ROLE == CR_GENERAL) == !ROLES, "roles on the production ring only");
+            const int slot = S >= 0 ? S : st.item % NST;
             const bool stamp_tile = t == (int)blockIdx.x;
             item_stamp(L, stamp_tile, ch, 0, K::WM);
             // ---- top of item: this item's DMA has landed for every wave ----
+            bool ring_ok = true;  // (tuning builds: the immediate wait's premise holds)
+            if constexpr (ROLE == CR_FIRST) {
+                if (st.staged < st.item) {
+                    // not staged (the previous tile's outputs lie in this tile's neighbourhood): drain,
+                    // publish, wait, stage
+                    force_publish(c, st);
+                    if (first_new == 0 && !dep_ok) {
+                        wait_deps(t, need);
+                        dep_ok = true;
+                    }
+                    st.issued += stage_chunk(c, me, 0, slot, true, bslot);
+                    st.staged = st.item;
+                    st.m0 = st.issued;
+                }
+                xn += c.pstride;  // chunk 0 is staged: the next chunk to stage is chunk 1
+                wo += WPC * 1024;
+                wait_vm_coarse(st.issued - st.m0);
+            } else if constexpr (ROLE != CR_GENERAL) {
+#ifdef ISR_TUNING
+                // tuning-build check of the immediate wait: nothing was issued since this chunk's DMA.
+                // A violation gives the launch up (the host raises) and the chunk issues no refill.
+                if (st.issued != st.m0) {
+                    ring_ok = false;
+                    if (threadIdx.x == 0) {
+                        __hip_atomic_store(c.state + 1, c.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_fetch_add(c.state + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+#endif
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            } else {
             if (st.staged < st.item) {
                 // not staged (the next tile needed this tile's own outputs): drain, publish, wait, stage
                 force_publish(c, st);
@@ -595,15 +748,18 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                 push_mark(st);
             }
             wait_vm(st.issued - st.m0);
+            }
             item_stamp(L, stamp_tile, ch, 1, K::WM);
             raw_barrier();
             item_stamp(L, stamp_tile, ch, 2, K::WM);
+            if constexpr (ROLE == CR_GENERAL || ROLE == CR_FIRST || ROLE == CR_SECOND) {
             if (st.pend_t >= 0 && (int)(st.m0 - st.pend_mark) >= 0) {  // its stores are older than this DMA
                 if (threadIdx.x == 0)
                     __hip_atomic_store(c.state + 4 + st.pend_t, st.pend_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 st.pend_t = -1;
             }
-            if (ch == 0) {
+            }
+            if (ROLE == CR_FIRST || (ROLE == CR_GENERAL && ch == 0)) {
                 trunk_stamp(L, t, c.ntiles, 1);
                 // bias → accumulators (register g of lane l: cout (g&3) + 8(g>>2) + 4hh of fragment f)
                 const float* bs = reinterpret_cast<const float*>(smem + K::BIAS_OFF + bslot * 256);
@@ -674,6 +830,41 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
             // (an earlier one in the same pass is issued at once, when a later one follows). ----
             Refill rf;
             rf.on = false;
+            const bool last = ROLE == CR_LAST || (ROLE == CR_LOOP && ch == nch - 1);
+            if constexpr (ROLE == CR_LAST || ROLE == CR_LOOP) {
+                // the next item's chunk 0 (with its bias), unless it needs this tile's own outputs
+                if (last && nx_exists && ring_ok) {
+                    const_rec& nrec = recs[nxL];
+                    bool go = true;
+                    if (nxL > 0 && rec_first_new(nrec) == 0) {
+                        if (tiles_adjacent(c, t, nxt)) {
+                            go = false;  // staged at its own top
+                        } else {
+                            wait_deps(nxt, c.gen * 1024u + (unsigned)nxL);
+                            st.dep_next = true;
+                        }
+                    }
+                    if (go) {
+                        st.issued += stage_chunk(c, src_of(c, nrec, nxt), 0, slot ^ 1, true, (bslot + 1) & 3);
+                        ++st.staged;
+                        st.m1 = st.issued;
+                    }
+                }
+            }
+            if constexpr (ROLE != CR_GENERAL && ROLE != CR_LAST) {
+                if constexpr (ROLE != CR_STEADY) {
+                    if (!last && ch + 1 >= first_new && !dep_ok) {
+                        wait_deps(t, need);
+                        dep_ok = true;
+                    }
+                }
+                if (!last && ring_ok) {
+                    st.issued += stage_own(slot ^ 1);
+                    ++st.staged;
+                    st.m1 = st.issued;
+                }
+            }
+            if constexpr (ROLE == CR_GENERAL)
             while (st.staged < st.item + NST - 1) {
                 const int off = st.staged + 1 - first_item;  // chunk offset from this tile's chunk 0
                 const int nslot = (st.staged + 1) % NST;
@@ -789,22 +980,69 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
 #endif
             item_stamp(L, stamp_tile, ch, 4, K::WM);
             pop_mark(st);  // the FIFO head moves to the next item (marks are positions from st.item)
+            ++st.item;
     };
-    int ch0 = 0;
-    if constexpr (NF == 2) {
-        if (fold && nch >= 4) {
-            do_chunk(0, TIC<0>{});
-            ++st.item;
-            do_chunk(1, TIC<1>{});
-            ++st.item;
-            do_chunk(2, TIC<2>{});
-            ++st.item;
-            do_chunk(3, TIC<3>{});
-            ++st.item;
-            ch0 = 4;
+    if constexpr (ROLES) {
+        // a chunk in the slot the stream has reached (a tile starts on either slot: counts may be odd)
+        int ch = 0;
+        auto in_slot = [&](auto fc_tag, auto role_tag) {
+            if constexpr (!FULL) do_chunk(ch, fc_tag, TIC<-1>{}, role_tag);
+            else if (st.item & 1) do_chunk(ch, fc_tag, TIC<1>{}, role_tag);
+            else do_chunk(ch, fc_tag, TIC<0>{}, role_tag);
+            ++ch;
+        };
+        if constexpr (NF == 2) {
+            if (fold) {  // the residual fold's chunks 0-3, peeled
+                in_slot(TIC<0>{}, TIC<CR_FIRST>{});
+                in_slot(TIC<1>{}, TIC<CR_SECOND>{});
+                in_slot(TIC<2>{}, TIC<CR_DEP>{});
+                in_slot(TIC<3>{}, TIC<CR_LOOP>{});  // the last chunk of a 64-channel input
+            }
         }
+        if (ch == 0) {
+            in_slot(TIC<-1>{}, TIC<CR_FIRST>{});
+            in_slot(TIC<-1>{}, TIC<CR_SECOND>{});
+        }
+        if (ch < nch) {
+            // steady chunks [ch, nch - 1), split at the chunk `wb` whose refill stages chunk first_new
+            const int wb = first_new - 1;
+            int stop = wb >= ch && wb < nch - 1 ? wb : nch - 1;
+            if constexpr (!FULL) {
+                for (; ch < nch; ++ch) do_chunk(ch, TIC<-1>{}, TIC<-1>{}, TIC<CR_LOOP>{});
+            } else {
+                for (;;) {
+                    if (ch < stop && (st.item & 1)) {  // peel: the run starts on slot 1
+                        do_chunk(ch, TIC<-1>{}, TIC<1>{}, TIC<CR_STEADY>{});
+                        ++ch;
+                    }
+                    for (; ch + 1 < stop; ch += 2) {
+                        do_chunk(ch, TIC<-1>{}, TIC<0>{}, TIC<CR_STEADY>{});
+                        do_chunk(ch + 1, TIC<-1>{}, TIC<1>{}, TIC<CR_STEADY>{});
+                    }
+                    if (ch < stop) {  // peel: an odd count
+                        do_chunk(ch, TIC<-1>{}, TIC<0>{}, TIC<CR_STEADY>{});
+                        ++ch;
+                    }
+                    if (ch >= nch - 1) break;
+                    in_slot(TIC<-1>{}, TIC<CR_DEP>{});
+                    stop = nch - 1;
+                }
+                in_slot(TIC<-1>{}, TIC<CR_LAST>{});
+            }
+        }
+    } else {
+        int ch0 = 0;
+        if constexpr (NF == 2) {
+            if (fold && nch >= 4) {
+                do_chunk(0, TIC<0>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
+                do_chunk(1, TIC<1>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
+                do_chunk(2, TIC<2>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
+                do_chunk(3, TIC<3>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
+                ch0 = 4;
+            }
+        }
+        for (int ch = ch0; ch < nch; ++ch) do_chunk(ch, TIC<-1>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
     }
-    for (int ch = ch0; ch < nch; ++ch, ++st.item) do_chunk(ch, TIC<-1>{});
     trunk_stamp(L, t, c.ntiles, 2);
 
     // the neighbourhood must be done with layer L-1 before this tile's outputs land (a layer
@@ -942,32 +1180,12 @@ __global__ __launch_bounds__(K::NT, K::WPS) void trunk_kernel(TrunkArgs a) {
         for (int L = 0; L < a.nl; ++L) {
             const_rec& rec = recs[L];
             for (int t = b; t < c.ntiles; t += G) {
-                Next nx;
-                nx.exists = true;
-                if (t + G < c.ntiles) {
-                    nx.L = L;
-                    nx.t = t + G;
-                } else if (L + 1 < a.nl) {
-                    nx.L = L + 1;
-                    nx.t = b;
-                } else {
-                    nx.exists = false;
-                    nx.L = L;
-                    nx.t = t;
-                }
-                const_rec& nrec = recs[nx.L];
-                nx.src = src_of(c, nrec, nx.t);
-                nx.first_new = rec_first_new(nrec);
-                nx.nch = rec_nch(nrec);
-                {
-                    const int bx = t % c.nbx, tq = t / c.nbx, by = tq % c.nby, im = tq / c.nby;
-                    const int bx2 = nx.t % c.nbx, nq = nx.t / c.nbx, by2 = nq % c.nby, im2 = nq / c.nby;
-                    nx.self_dep = im == im2 && abs(bx - bx2) <= 1 && abs(by - by2) <= 1;
-                }
+                int nxL, nxt;
+                const bool nx_exists = next_item(L, t, b, G, c.ntiles, a.nl, nxL, nxt);
                 const int kind = rec_kind(rec);
-                if (kind == 0) run_tile<K, 1, false, H>(c, st, rec, L, t, nx);
-                else if (kind == 2) run_tile<K, 1, true, H>(c, st, rec, L, t, nx);  // the backward chain's gathers
-                else run_tile<K, 2, false, H>(c, st, rec, L, t, nx);
+                if (kind == 0) run_tile<K, 1, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
+                else if (kind == 2) run_tile<K, 1, true, H>(c, st, recs, L, t, nxL, nxt, nx_exists);  // the backward chain's gathers
+                else run_tile<K, 2, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
             }
         }
     }

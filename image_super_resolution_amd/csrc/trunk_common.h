@@ -143,6 +143,15 @@ __device__ __forceinline__ void wait_vm(uint32_t n) {
 #undef ISR_VMW
 }
 
+// The same wait for a tile's first chunk on the 2-slot ring, rounded DOWN to 16, 8 or 0 (waiting
+// for fewer outstanding operations than allowed is always correct; timing only): behind that
+// chunk's DMA are the previous tile's epilogue stores, 8 (32 couts) or 16 (64 couts) per wave.
+__device__ __forceinline__ void wait_vm_coarse(uint32_t n) {
+    if (n >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    else if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 template <int V> struct TIC { static constexpr int value = V; };
 
 // A operand of the residual fold: (1/s1) I on couts [16 h16, 16 h16 + 16) of a 32-cout
