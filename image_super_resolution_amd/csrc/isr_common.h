@@ -67,6 +67,24 @@ __device__ __forceinline__ bf16x8 pack8(const float* x) {
     }
 }
 
+// pack8 through the packed converts, two floats per instruction (v_cvt_pk_f16_f32 /
+// v_cvt_pk_bf16_f32 on gfx950): the same round-to-nearest-even, so the same bits as pack8
+template <bool H>
+__device__ __forceinline__ bf16x8 pack8_pairs(const float* x) {
+    typedef __attribute__((ext_vector_type(2))) float f32x2;
+    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    u32x4 t;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const f32x2 p = {x[2 * d], x[2 * d + 1]};
+        if constexpr (H) t[d] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, f16x2));
+        else t[d] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, bf16x2));
+    }
+    return __builtin_bit_cast(bf16x8, t);
+}
+
 // the storage bits of one float (16 bits, in the low half)
 template <bool H>
 __device__ __forceinline__ uint16_t bits16(float x) {

@@ -113,7 +113,14 @@ __global__ __launch_bounds__(1024) void trunk_prep_kernel(const isr_conv_desc* l
         rec.planes = (uint32_t)(d.x.coff / 16) | (uint32_t)(d.y.coff / 16) << 16;
         rec.shape = (uint32_t)((masked ? d.m.coff : d.r2.coff) / 16) | (uint32_t)(d.cin / 16) << 16 |
                     (uint32_t)(kind & 255) << 24;
-        rec.deps = (uint32_t)first_new | (uint32_t)fold << 8 | (uint32_t)idv << 16;
+        // the tile epilogue's form: what the general body tests per value, decided once here
+        // (comparisons with a NaN slope or scale are false: such a layer stays general)
+        int form = EPI_GENERAL;
+        if (kind == 0 && !d.r1.data && !d.r2.data && d.s2 == 1.f && d.slope > 0.f && d.slope < 1.f)
+            form = EPI_GROWTH;
+        else if (kind == 1 && fold && d.slope == 1.f)
+            form = d.r2.data ? EPI_FINAL_R2 : (d.s2 == 1.f ? EPI_FINAL : EPI_FINAL_S2);
+        rec.deps = (uint32_t)first_new | (uint32_t)fold << 8 | (uint32_t)form << 9 | (uint32_t)idv << 16;
         rec.slope = masked ? d.mslope : d.slope;
         rec.s1 = d.s1;
         rec.s2 = d.s2;
@@ -1050,7 +1057,27 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
     if (!dep_ok && first_new != tk::NEED_NONE) wait_deps(t, need);
 
     // ---- epilogue: straight from the accumulators, write-through (sc1) stores ----
-    {
+    // EF = the layer's epilogue form (trunk_common.h EPI_*, classified by the prep kernel), FT = the
+    // tile lies wholly inside the image.  EPI_GENERAL decides slope, fold, r2, mask, s2 and `valid`
+    // per value at run time; the other forms carry only their own arithmetic, convert with the packed
+    // instruction, and zero a ragged tile's outside pixels on the packed dwords (0.f packs to 0).
+    // Every form gives the general body's bits: the LeakyReLU stays the general body's compare and
+    // select (a >= 0 ? a : a * slope; hipcc canonicalises the inputs of a float max with one more
+    // v_max each, so max(a, a * slope) costs the same 2.5 instructions per value and would still have
+    // to be argued for -0 and NaN); the fold layers have slope == 1; u * s2 + r2 is one fused
+    // multiply-add in the general body (hipcc contracts it) and an explicit one here.
+    auto epilogue = [&](auto form_tag, auto full_tag) {
+        constexpr int EF = decltype(form_tag)::value;
+        constexpr bool GEN = EF == EPI_GENERAL, FT = decltype(full_tag)::value != 0;
+        static_assert(GEN || (EF == EPI_GROWTH ? NF == 1 && !MASKED : NF == 2), "form and layer kind");
+        const bool use_r2 = GEN ? (has_r2 || masked) : EF == EPI_FINAL_R2;
+        // the body's marker in the assembly (tools/trunk_isa_mix.py) and the LeakyReLU's 0.0f as a
+        // value of this body alone: compared with the literal, the 64 compares of a growth tile were
+        // hoisted above the branch between the full and the ragged body, and their lane masks held
+        // in 128 SGPRs, most of them spilled
+        float zero = 0.f;
+        if constexpr (EF == EPI_GROWTH) asm volatile("; trunk epilogue form %1 full %2" : "+s"(zero) : "n"(EF), "n"((int)FT));
+        else if constexpr (!GEN) asm volatile("; trunk epilogue form %0 full %1" ::"n"(EF), "n"((int)FT));
         typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
         const int xx = x0 + l31;
         const float slope = rec.slope, s1 = rec.s1, s2 = rec.s2;
@@ -1076,18 +1103,42 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                 }
             st.issued += NF * 2;
         };
-        if (has_r2 || masked) load_r2(0);
+        if (use_r2) load_r2(0);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if ((has_r2 || masked) && r + 1 < R) load_r2(r + 1);
+            if (use_r2 && r + 1 < R) load_r2(r + 1);
             const int yy = y0 + wave * R + r;
             const bool valid = yy < c.h && xx < c.w;
             const uint32_t pix = (uint32_t)((yy + c.pad) * c.wp + xx + c.pad);
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 float v[16];
+                if constexpr (GEN) {
 #pragma unroll
-                for (int g = 0; g < 16; ++g) v[g] = acc[r][f][g];
+                    for (int g = 0; g < 16; ++g) v[g] = acc[r][f][g];
+                } else {
+                    // what does not depend on the pixel (activation, s1, s2) on the accumulator
+                    // pairs before the lane swap: packed multiplies into fresh registers, which the
+                    // swap then changes in place (swapping first cost a copy per accumulator)
+                    typedef __attribute__((ext_vector_type(2))) float f32x2;
+                    const f32x16& a = acc[r][f];
+#pragma unroll
+                    for (int g = 0; g < 16; g += 2) {
+                        f32x2 p = {a[g], a[g + 1]};
+                        if constexpr (EF == EPI_GROWTH) {
+                            p = p * slope;
+                        } else {
+                            p = p * s1;
+                            if constexpr (EF == EPI_FINAL_S2) p = p * s2;
+                        }
+                        v[g] = p[0];
+                        v[g + 1] = p[1];
+                    }
+                    if constexpr (EF == EPI_GROWTH) {
+#pragma unroll
+                        for (int g = 0; g < 16; ++g) v[g] = a[g] >= zero ? a[g] : v[g];
+                    }
+                }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     swap_halves(v[k], v[4 + k]);
@@ -1098,6 +1149,9 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                     float* u = v + 8 * blk;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
+                        if constexpr (!GEN) {
+                            if constexpr (EF == EPI_FINAL_R2) u[e] = __builtin_fmaf(u[e], s2, elt<H>(q2[r][f][blk], e));
+                        } else {
                         if (masked)
                             u[e] = elt<H>(q2[r][f][blk], e) > 0.f ? u[e] : u[e] * slope;
                         else
@@ -1109,10 +1163,22 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                             if (scale2) u[e] *= s2;
                         }
                         if (!valid) u[e] = 0.f;
+                        }
                     }
                     const auto yr = rsrc_n(ybase + (size_t)(2 * f + blk) * c.pstride, c.pstride);
                     const uint32_t off = pix * 32 + 16 * hh;
-                    const bf16x8 tq = pack8<H>(u);
+                    bf16x8 tq;
+                    if constexpr (GEN) {
+                        tq = pack8<H>(u);
+                    } else {
+                        tq = pack8_pairs<H>(u);
+                        if constexpr (!FT) {
+                            u32x4 z = __builtin_bit_cast(u32x4, tq);
+#pragma unroll
+                            for (int d = 0; d < 4; ++d) z[d] = valid ? z[d] : 0u;
+                            tq = __builtin_bit_cast(bf16x8, z);
+                        }
+                    }
                     if (!(c.abl & 4)) {
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tq), yr, off, 0, K::STORE_AUX);
                         ++st.issued;
@@ -1120,6 +1186,23 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                 }
             }
         }
+    };
+    // one wave-uniform branch per tile into the body of the layer's form (production ring only)
+    auto epilogue_of = [&](auto form_tag) {
+        if (y0 + K::TH <= c.h && x0 + tk::TW <= c.w) epilogue(form_tag, TIC<1>{});
+        else epilogue(form_tag, TIC<0>{});
+    };
+    const int form = ROLES ? rec_form(rec) : (int)EPI_GENERAL;
+    if constexpr (ROLES && NF == 1) {
+        if (form == EPI_GROWTH) epilogue_of(TIC<EPI_GROWTH>{});
+        else epilogue(TIC<EPI_GENERAL>{}, TIC<0>{});
+    } else if constexpr (ROLES) {
+        if (form == EPI_FINAL) epilogue_of(TIC<EPI_FINAL>{});
+        else if (form == EPI_FINAL_R2) epilogue_of(TIC<EPI_FINAL_R2>{});
+        else if (form == EPI_FINAL_S2) epilogue_of(TIC<EPI_FINAL_S2>{});
+        else epilogue(TIC<EPI_GENERAL>{}, TIC<0>{});
+    } else {
+        epilogue(TIC<EPI_GENERAL>{}, TIC<0>{});
     }
     trunk_stamp(L, t, c.ntiles, 3);
     st.pend_t = t;

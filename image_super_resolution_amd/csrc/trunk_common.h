@@ -21,12 +21,23 @@ struct TrunkRec {
     uint64_t x, y, w, b, r2;   // buffer bases, packed weights, fp32 bias, r2 base (or 0)
     uint32_t planes;           // xp | yp << 16: first 16-channel plane of x / y (coff / 16)
     uint32_t shape;            // r2p | nch << 16 | kind << 24 (nch = cin / 16; kind 0 growth, 1 final)
-    uint32_t deps;             // first_new | fold << 8 | idv << 16 (first chunk the previous layer
-                               // wrote, NEED_NONE on layer 0; fold: r1 == x[0:cout] added as x/s1
-                               // by MFMA; idv: bf16 bits of 1/s1)
+    uint32_t deps;             // first_new | fold << 8 | form << 9 | idv << 16 (first chunk the
+                               // previous layer wrote, NEED_NONE on layer 0; fold: r1 == x[0:cout]
+                               // added as x/s1 by MFMA; form: the tile epilogue's form, EPI_*, 3
+                               // bits; idv: storage-type bits of 1/s1)
     float slope, s1, s2;
 };
 static_assert(sizeof(TrunkRec) == 64, "record size");
+
+// Tile-epilogue forms (rec.deps bits 9-11), classified by the prep kernel.  The production ring
+// compiles one body per form; EPI_GENERAL decides everything per value at run time.
+enum : int {
+    EPI_GENERAL,   // any validated layer: slope, fold, r2, mask and s2 tested per value
+    EPI_GROWTH,    // kind 0, s2 == 1, 0 < slope < 1: v = max(acc, acc * slope)
+    EPI_FINAL,     // kind 1 with the fold, no r2, s2 == 1: v = acc * s1
+    EPI_FINAL_S2,  // the same with s2 != 1: v = acc * s1 * s2
+    EPI_FINAL_R2   // kind 1 with the fold and r2: v = fma(acc * s1, s2, r2)
+};
 
 // Geometry (16 words just before the layer records), shared by every layer.
 struct TrunkGeo {
@@ -49,6 +60,7 @@ __device__ __forceinline__ int rec_nch(const_rec_t& r) { return (int)((r.shape >
 __device__ __forceinline__ int rec_kind(const_rec_t& r) { return (int)(r.shape >> 24); }
 __device__ __forceinline__ int rec_first_new(const_rec_t& r) { return (int)(r.deps & 255); }
 __device__ __forceinline__ bool rec_fold(const_rec_t& r) { return ((r.deps >> 8) & 1) != 0; }
+__device__ __forceinline__ int rec_form(const_rec_t& r) { return (int)((r.deps >> 9) & 7); }
 __device__ __forceinline__ uint32_t rec_idv(const_rec_t& r) { return r.deps >> 16; }
 
 __device__ __forceinline__ void raw_barrier() {

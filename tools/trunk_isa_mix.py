@@ -4,8 +4,10 @@
 Compiles trunk.hip to gfx950 device assembly with the flags of the library build (_build.FLAGS,
 _build.HIPCC) and prints, for each production instantiation of trunk_kernel (the fp16 and the bf16
 pair form): per basic block that holds MFMAs or vector-memory instructions the instruction count by
-class, the totals over the whole kernel, and the compiler's resource lines
-(-Rpass-analysis=kernel-resource-usage: registers, spills, scratch, occupancy).
+class, the totals over the whole kernel, the compiler's resource lines
+(-Rpass-analysis=kernel-resource-usage: registers, spills, scratch, occupancy), and one line per
+basic block that holds vector-memory stores (the tile epilogues): instructions, stores, VALU
+instructions per stored value, and which specialised epilogue form the block belongs to.
 
     python tools/trunk_isa_mix.py [--csrc DIR] [-D NAME=VALUE ...] [--all-blocks]
 
@@ -101,6 +103,59 @@ def blocks(lines: list[str]) -> list[tuple[str, Counter]]:
     return res
 
 
+EPI_FORMS = {1: "growth", 2: "final", 3: "final_s2", 4: "final_r2"}  # trunk_common.h EPI_*
+EPI_MARK = re.compile(r"^; trunk epilogue form (\d+) full (\d+)")
+STORE = re.compile(r"^(?:buffer|global|flat)_store_(\w+)")
+STORE_BYTES = {"byte": 1, "short": 2, "dword": 4, "dwordx2": 8, "dwordx3": 12, "dwordx4": 16}
+PACKED_CVT = {"fp16": "v_cvt_pk_f16_f32", "bf16": "v_cvt_pk_bf16_f32"}
+
+
+def store_blocks(lines: list[str]) -> list[dict]:
+    """One entry per basic block that holds vector-memory stores: its instruction count, stores,
+    stored 16-bit values per lane, VALU instructions (MFMAs and lane moves apart) per stored value,
+    the packed fp32 -> 16-bit converts in it, and the epilogue form whose marker comment
+    (run_tile's specialised bodies emit one) lies in the block: (name, full tile) or None."""
+    res, cur = [], None
+
+    def new(name):
+        return {"block": name, "insts": 0, "stores": 0, "values": 0, "valu": 0, "ops": Counter(), "form": None}
+
+    def close(b):
+        # tile-epilogue blocks only: a block whose stores are single dwords holds a progress word
+        if b and b["values"] >= 8:
+            b["valu_per_value"] = b["valu"] / b["values"]
+            res.append(b)
+
+    cur = new("entry")
+    for line in lines:
+        s = line.strip()
+        m = re.match(r"^(\.LBB\d+_\d+):", s) or re.match(r"^; %bb\.(\d+):", s)
+        if m:
+            close(cur)
+            cur = new(m.group(1))
+            continue
+        m = EPI_MARK.match(s)
+        if m:
+            cur["form"] = (EPI_FORMS.get(int(m.group(1)), m.group(1)), bool(int(m.group(2))))
+            continue
+        if not s or s.startswith((";", ".", "//")):
+            continue
+        op = s.split()[0]
+        c = classify(op)
+        if not c:
+            continue
+        cur["insts"] += 1
+        cur["ops"][op.removesuffix("_e32").removesuffix("_e64")] += 1
+        if c == "valu":
+            cur["valu"] += 1
+        m = STORE.match(op)
+        if m:
+            cur["stores"] += 1
+            cur["values"] += STORE_BYTES.get(m.group(1), 0) // 2
+    close(cur)
+    return res
+
+
 def resources(remarks: str) -> dict[str, list[str]]:
     out, cur = {}, None
     for line in remarks.splitlines():
@@ -114,6 +169,22 @@ def resources(remarks: str) -> dict[str, list[str]]:
         elif cur is not None:
             cur.append(t)
     return out
+
+
+def storage_of(name: str) -> str:
+    return "fp16" if PROD.match(name).group(1) == "1" else "bf16"
+
+
+def production_store_blocks(csrc: Path = _build.CSRC, defines: tuple[str, ...] = ()) -> dict[str, list[dict]]:
+    """storage ("fp16" / "bf16") -> store_blocks() of that production instantiation."""
+    asm, _ = device_asm(Path(csrc).resolve(), list(defines))
+    return {storage_of(name): store_blocks(lines) for name, lines in kernels(asm).items()}
+
+
+def fmt_store_block(b: dict, storage: str) -> str:
+    form = "-" if b["form"] is None else f"{b['form'][0]}/{'full' if b['form'][1] else 'ragged'}"
+    return (f"{b['block']:>12} {form:>16} {b['insts']:6d} {b['stores']:6d} {b['values']:6d} {b['valu']:6d} "
+            f"{b['valu_per_value']:8.2f} {b['ops'].get(PACKED_CVT[storage], 0):6d}")
 
 
 def fmt(cnt: Counter) -> str:
@@ -133,7 +204,7 @@ def main() -> int:
         print("no production trunk_kernel instantiation found", file=sys.stderr)
         return 1
     for name, lines in ks.items():
-        storage = "fp16" if PROD.match(name).group(1) == "1" else "bf16"
+        storage = storage_of(name)
         bl = blocks(lines)
         print(f"== {name} ({storage} storage)")
         for t in res.get(name, []):
@@ -149,6 +220,11 @@ def main() -> int:
         mf = [c for _, c in bl if c.get("mfma")]
         lane_in = sum(c.get("lane", 0) for c in mf)
         print(f"   MFMA blocks: {len(mf)}, lane moves (v_readlane / v_writelane / v_readfirstlane) inside them: {lane_in}")
+        print("   store-holding blocks (values = stored 16-bit values per lane; pk_cvt = packed fp32 converts):")
+        print(f"   {'block':>12} {'epilogue form':>16} {'insts':>6} {'stores':>6} {'values':>6} {'valu':>6} "
+              f"{'valu/val':>8} {'pk_cvt':>6}")
+        for b in store_blocks(lines):
+            print("   " + fmt_store_block(b, storage))
         print()
     return 0
 
