@@ -5,11 +5,9 @@ link.  The output lands in image_super_resolution_amd/lib/ so it travels with
 the repository snapshot to the GPU box.
 
 `python -m image_super_resolution_amd._build --tuning` builds lib/libisr_tuning.so
-with -DISR_TUNING (adds timing-only ablation variants whose outputs are wrong);
-tools load it with ISR_LIB=<path>.  The production libisr.so never contains them.
-`--interleave` builds lib/libisr_interleave.so: the production objects with trunk.hip rebuilt
-under -DISR_TRUNK_INTERLEAVE=1 (the trunk's refill pieces issued one per step-0 MFMA; kept for
-the parity run tests/test_gpu_chain.py gets with ISR_LIB pointing at it).
+with -DISR_TUNING (the shipping kernels instrumented: stamps, ablation knobs, ring-protocol
+checks; plus A/B forms of the per-conv and weight-gradient kernels); tools load it with
+ISR_LIB=<path>.  The production libisr.so never contains them.
 """
 from __future__ import annotations
 
@@ -85,8 +83,8 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
         asm = check_lds_waits.device_asm(src, ["-DISR_TUNING"] if tuning else [])
         errs = check_lds_waits.check_asm(asm, src.name)
         if tuning and errs:
-            # the tuning library also carries A/B forms that never ship (measured slower; some are
-            # timing probes): a hazard there is reported, and fatal only in a production kernel
+            # the tuning library also carries A/B forms of the weight-gradient kernels that never ship
+            # (measured slower): a hazard there is reported, and fatal only in a production kernel
             prod = set(check_lds_waits.kernels(check_lds_waits.device_asm(src, []))[0])
             for e in errs:
                 if e.split(":", 1)[0] not in prod:
@@ -110,71 +108,5 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
     return lib_path
 
 
-def build_interleave(verbose: bool = False) -> Path:
-    """libisr_interleave.so: production objects, trunk.hip with -DISR_TRUNK_INTERLEAVE=1."""
-    build(verbose=verbose)
-    objdir = PKG / "build_interleave"
-    objdir.mkdir(exist_ok=True)
-    trunk_obj = objdir / "trunk.o"
-    cmd = [HIPCC, *FLAGS, "-DISR_TRUNK_INTERLEAVE=1", "-c", str(CSRC / "trunk.hip"), "-o", str(trunk_obj)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed on trunk.hip (interleave):\n{r.stderr}")
-    objs = [trunk_obj if src.stem == "trunk" else PKG / "build" / (src.stem + ".o") for src in sources()]
-    lib_path = LIBDIR / "libisr_interleave.so"
-    tmp = lib_path.with_suffix(".so.tmp")
-    r = subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(tmp), *map(str, objs)],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stderr}")
-    os.replace(tmp, lib_path)
-    return lib_path
-
-
-def build_probe16(verbose: bool = False) -> Path:
-    """libisr_probe16.so: production objects, trunk.hip with -DISR_TRUNK_MFMA16_PROBE=1 (timing
-    probe, outputs wrong: each growth-chunk MFMA as two 16x16x32 of the same FLOPs)."""
-    build(verbose=verbose)
-    objdir = PKG / "build_probe16"
-    objdir.mkdir(exist_ok=True)
-    trunk_obj = objdir / "trunk.o"
-    cmd = [HIPCC, *FLAGS, "-DISR_TRUNK_MFMA16_PROBE=1", "-c", str(CSRC / "trunk.hip"), "-o", str(trunk_obj)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed on trunk.hip (probe16):\n{r.stderr}")
-    objs = [trunk_obj if src.stem == "trunk" else PKG / "build" / (src.stem + ".o") for src in sources()]
-    lib_path = LIBDIR / "libisr_probe16.so"
-    r = subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(lib_path), *map(str, objs)],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stderr}")
-    return lib_path
-
-
-def build_trunk_alt(tag: str, defines: list[str], verbose: bool = False) -> Path:
-    """lib/libisr_<tag>.so: the production objects with trunk.hip rebuilt under `defines` (A/B of a
-    production trunk option in alternating processes, e.g. tag "xcd", ["-DISR_TRUNK_XCD=1"])."""
-    build(verbose=verbose)
-    objdir = PKG / f"build_{tag}"
-    objdir.mkdir(exist_ok=True)
-    trunk_obj = objdir / "trunk.o"
-    r = subprocess.run([HIPCC, *FLAGS, *defines, "-c", str(CSRC / "trunk.hip"), "-o", str(trunk_obj)],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed on trunk.hip ({tag}):\n{r.stderr}")
-    objs = [trunk_obj if src.stem == "trunk" else PKG / "build" / (src.stem + ".o") for src in sources()]
-    lib_path = LIBDIR / f"libisr_{tag}.so"
-    r = subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(lib_path), *map(str, objs)],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stderr}")
-    return lib_path
-
-
 if __name__ == "__main__":
-    if "--probe16" in sys.argv:
-        print(build_probe16(verbose=True))
-    elif "--interleave" in sys.argv:
-        print(build_interleave(verbose=True))
-    else:
-        print(build(force="--force" in sys.argv, verbose=True, tuning="--tuning" in sys.argv))
+    print(build(force="--force" in sys.argv, verbose=True, tuning="--tuning" in sys.argv))

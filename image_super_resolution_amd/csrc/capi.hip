@@ -11,12 +11,8 @@ namespace isr {
 int conv3x3_fwd_dispatch(const isr_conv_desc* d, hipStream_t s);
 int conv3x3_fwd_variant(const isr_conv_desc* d, int variant, hipStream_t s);
 int conv_stamps_set(void* p);
-int chain_knobs_set(const int* k);
-int tail_stamps_set(void* p);
-size_t conv_chain_state_words(int n, int ha, int wa);
-int conv_chain(const isr_chain_desc* c, hipStream_t s);
 size_t trunk_state_words(int n, int ha, int wa);
-int trunk_launch(const isr_chain_desc* c, hipStream_t s, int form);
+int trunk_launch(const isr_chain_desc* c, hipStream_t s);
 int trunk_stamps_set(void* p);
 int trunk_knobs_set(const int* k);
 int trunk_item_stamps_set(void* p);
@@ -293,11 +289,14 @@ int isr_conv3x3_wino_fwd(const isr_conv_desc* d, isr_stream_t s) {
     return launched(isr::conv3x3_wino_fwd_dispatch(d, (hipStream_t)s), "conv3x3_wino");
 }
 
+// (the round-2 chain's progress words, (tiles + 7) / 4 * 4, were always fewer than the trunk's)
 size_t isr_conv_chain_state_words(int32_t n, int32_t ha, int32_t wa) {
     if (n <= 0 || ha <= 0 || wa <= 0 || ha % 16 || wa % 32) return 0;
-    const size_t a = isr::conv_chain_state_words(n, ha, wa), b = isr::trunk_state_words(n, ha, wa);
-    return a > b ? a : b;
+    return isr::trunk_state_words(n, ha, wa);
 }
+
+// The A/B forms that lost against a shipping kernel were removed from both builds.
+#define ISR_REMOVED_FORM "is a removed A/B form (its measurements: DESIGN.md section 5)"
 
 int isr_conv_chain_variant(const isr_chain_desc* c, int32_t variant, isr_stream_t s) {
     if (!c || !c->layers || !c->kinds || !c->state || c->nl <= 0 || c->nl > 1024)
@@ -305,25 +304,11 @@ int isr_conv_chain_variant(const isr_chain_desc* c, int32_t variant, isr_stream_
     if (c->n <= 0 || c->ha <= 0 || c->wa <= 0 || c->ha % 16 || c->wa % 32)
         return fail(ISR_ERR_BAD_DESC, "conv chain: bad grid n=%d ha=%d wa=%d", c->n, c->ha, c->wa);
     if (c->f16 != 0 && c->f16 != 1) return fail(ISR_ERR_BAD_DESC, "conv chain: f16 must be 0 or 1");
-    if (c->f16 && variant != 0)
-        return fail(ISR_ERR_UNSUPPORTED, "conv chain: fp16 storage runs the production trunk form (variant 0) only");
-    if (variant == 4 || variant == 9)
-        return fail(ISR_ERR_UNSUPPORTED, "conv chain: variant %d (a losing A/B form) was removed in round 6", variant);
-    if (variant == 0 || (variant >= 2 && variant <= 8)) {
-        static const int form_of[10] = {0, 0, 1, 2, 3, 4, 5, 6, 7, 8};
-        const int rc = isr::trunk_launch(c, (hipStream_t)s, form_of[variant]);
-        if (rc == -3) return fail(ISR_ERR_UNSUPPORTED, "conv chain: variant %d is an A/B form of the tuning library "
-                                  "(lib/libisr_tuning.so)", variant);
-        if (rc == -4) return fail(ISR_ERR_LAUNCH, "conv chain: the occupancy query admits no workgroup per CU");
-        if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "conv chain: unsupported grid or layer count");
-        return launched(rc, "conv chain");
-    }
-    if (variant == 1) {
-        const int rc = isr::conv_chain(c, (hipStream_t)s);
-        if (rc == -3) return fail(ISR_ERR_UNSUPPORTED, "conv chain: variant 1 (the round-2 kernel) is in the tuning library only");
-        return launched(rc, "conv chain (round-2 kernel)");
-    }
-    return fail(ISR_ERR_UNSUPPORTED, "conv chain: unknown variant %d", variant);
+    if (variant != 0) return fail(ISR_ERR_UNSUPPORTED, "conv chain: variant %d " ISR_REMOVED_FORM, variant);
+    const int rc = isr::trunk_launch(c, (hipStream_t)s);
+    if (rc == -4) return fail(ISR_ERR_LAUNCH, "conv chain: the occupancy query admits no workgroup per CU");
+    if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "conv chain: unsupported grid or layer count");
+    return launched(rc, "conv chain");
 }
 
 int isr_conv_chain(const isr_chain_desc* c, isr_stream_t s) { return isr_conv_chain_variant(c, 0, s); }
@@ -353,17 +338,12 @@ int isr_tuning_conv_stamps(void* buf) {
     return rc == 0 ? ISR_OK : fail(ISR_ERR_LAUNCH, "conv stamps: hipMemcpyToSymbol failed");
 }
 
-int isr_tuning_chain_knobs(int32_t delay_ticks, int32_t delay_shift, int32_t k2, int32_t k3) {
-    const int k[4] = {delay_ticks, delay_shift, k2, k3};
-    const int rc = isr::chain_knobs_set(k);
-    if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "chain knobs: library built without -DISR_TUNING");
-    return rc == 0 ? ISR_OK : fail(ISR_ERR_LAUNCH, "chain knobs: hipMemcpyToSymbol failed");
+int isr_tuning_chain_knobs(int32_t, int32_t, int32_t, int32_t) {
+    return fail(ISR_ERR_UNSUPPORTED, "chain knobs: the round-2 chain kernel that read them " ISR_REMOVED_FORM);
 }
 
-int isr_tuning_tail_stamps(void* buf) {
-    const int rc = isr::tail_stamps_set(buf);
-    if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "tail stamps: library built without -DISR_TUNING");
-    return rc == 0 ? ISR_OK : fail(ISR_ERR_LAUNCH, "tail stamps: hipMemcpyToSymbol failed");
+int isr_tuning_tail_stamps(void*) {
+    return fail(ISR_ERR_UNSUPPORTED, "tail stamps: the 4-wave tail walk that wrote them " ISR_REMOVED_FORM);
 }
 
 int isr_conv3x3_fwd_variant(const isr_conv_desc* d, int32_t variant, isr_stream_t s) {
@@ -411,9 +391,9 @@ int isr_tail9x9_fwd(const isr_tail_desc* d, isr_stream_t s) {
 int isr_tail9x9_fwd_variant(const isr_tail_desc* d, int32_t variant, isr_stream_t s) {
     const int rc = tail_validate(d);
     if (rc != ISR_OK) return rc;
-    const int r = isr::tail9x9_fwd_variant(d, variant, (hipStream_t)s);
-    if (r == -2) return fail(ISR_ERR_UNSUPPORTED, "tail9x9: no variant %d", variant);
-    return launched(r, "tail9x9");
+    if (variant != 0 && variant != 3 && variant != 5)
+        return fail(ISR_ERR_UNSUPPORTED, "tail9x9: variant %d " ISR_REMOVED_FORM, variant);
+    return launched(isr::tail9x9_fwd_variant(d, variant, (hipStream_t)s), "tail9x9");
 }
 
 static int wgrad_validate(const isr_wgrad_desc* d) {

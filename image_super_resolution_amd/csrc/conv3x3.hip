@@ -33,14 +33,14 @@ namespace isr {
 #ifdef ISR_TUNING
 __device__ unsigned long long* g_conv_stamps;
 #endif
-__device__ __forceinline__ void conv_stamp(int slot, int row = -1) {
+__device__ __forceinline__ void conv_stamp(int slot) {
 #ifdef ISR_TUNING
     unsigned long long* p = g_conv_stamps;
-    if (p != nullptr && threadIdx.x == 0 && row != -2) {
+    if (p != nullptr && threadIdx.x == 0) {
         unsigned long long t;
         asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");  // not hoistable
-        p[(size_t)(row < 0 ? blockIdx.x : row) * 8 + slot + threadIdx.x] = t;
-        if (slot == 0 && row < 0) {
+        p[(size_t)blockIdx.x * 8 + slot + threadIdx.x] = t;
+        if (slot == 0) {
             const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);   // HW_REG_HW_ID
             const unsigned xcc = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 20); // HW_REG_XCC_ID
             p[(size_t)blockIdx.x * 8 + 6 + threadIdx.x] = hw;
@@ -49,7 +49,6 @@ __device__ __forceinline__ void conv_stamp(int slot, int row = -1) {
     }
 #else
     (void)slot;
-    (void)row;
 #endif
 }
 
@@ -145,8 +144,8 @@ __device__ __forceinline__ bf16x8 fold_a(uint32_t idv, int h16) {
 
 // The fold applies when r1 is exactly the conv's own input channels [0, cout) (one cout tile),
 // the activation is the identity and 1/s1 is exact in bf16 (add_rate 0.2 → 5).
-template <class C, bool XS2, class Desc>
-__device__ __forceinline__ bool fold_ok(const Desc& d) {
+template <class C, bool XS2>
+__device__ __forceinline__ bool fold_ok(const isr_conv_desc& d) {
     if constexpr (!C::FOLD || C::NF != 2 || C::KS != 1 || C::TN != 3 || C::PIPE != 2 || XS2) {
         return false;
     } else {
@@ -171,8 +170,8 @@ __device__ __forceinline__ bool fold_ok(const Desc& d) {
 // MODE bits (compile-time: no per-element branches): 1 = r1, 2 = r2, 4 = y2, 8 = shuffle,
 // 16 = LeakyReLU' mask (backward).  r1_cn / m_c0 are multiples of 32, so their
 // channel tests are uniform per 32-cout fragment (scalar branches).
-template <class C, int MODE, int HX, class Desc>
-__device__ __forceinline__ void epilogue(const Desc& d, f32x16 (&acc)[C::R][C::NF], int img, int ct,
+template <class C, int MODE>
+__device__ __forceinline__ void epilogue(const isr_conv_desc& d, f32x16 (&acc)[C::R][C::NF], int img, int ct,
                                          int x0, int y0, int wave, int lane) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int R = C::R, NF = C::NF, CT = C::CT, EPS = C::EPS;
@@ -212,7 +211,7 @@ __device__ __forceinline__ void epilogue(const Desc& d, f32x16 (&acc)[C::R][C::N
                 }
                 if constexpr (MODE & 16) {  // LeakyReLU' of the (shuffled-grid) mask source, all channels
                     const bf16x8 mq =
-                        load16_hx<HX>(d.m, d.n, view_at(d.m, img, 2 * yy + si, 2 * x0 + xo, ct * (CT / 4) + cg * 8));
+                        load16(view_at(d.m, img, 2 * yy + si, 2 * x0 + xo, ct * (CT / 4) + cg * 8));
 #pragma unroll
                     for (int k = 0; k < 8; ++k)
                         if (!(elt<C::H>(mq, k) > 0.f)) v[k] *= d.mslope;
@@ -221,7 +220,7 @@ __device__ __forceinline__ void epilogue(const Desc& d, f32x16 (&acc)[C::R][C::N
 #pragma unroll
                     for (int k = 0; k < 8; ++k) v[k] = 0.f;
                 }
-                store8_bf16_hx<HX, C::H>(d.y, d.n, view_at(d.y, img, 2 * yy + si, 2 * x0 + xo, ct * (CT / 4) + cg * 8), v);
+                store8_t<C::H>(view_at(d.y, img, 2 * yy + si, 2 * x0 + xo, ct * (CT / 4) + cg * 8), v);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
@@ -249,11 +248,11 @@ __device__ __forceinline__ void epilogue(const Desc& d, f32x16 (&acc)[C::R][C::N
             for (int blk = 0; blk < 2; ++blk) {
                 const int co = cf + 16 * blk + 8 * hh;
                 if constexpr (MODE & 1) {
-                    if (use_r1) q1[buf][blk] = load16_hx<HX>(d.r1, d.n, view_at(d.r1, img, yy, xx, co));
+                    if (use_r1) q1[buf][blk] = load16(view_at(d.r1, img, yy, xx, co));
                 }
-                if constexpr (MODE & 2) q2[buf][blk] = load16_hx<HX>(d.r2, d.n, view_at(d.r2, img, yy, xx, co));
+                if constexpr (MODE & 2) q2[buf][blk] = load16(view_at(d.r2, img, yy, xx, co));
                 if constexpr (MODE & 16) {
-                    if (use_m) qm[buf][blk] = load16_hx<HX>(d.m, d.n, view_at(d.m, img, yy, xx, co));
+                    if (use_m) qm[buf][blk] = load16(view_at(d.m, img, yy, xx, co));
                 }
             }
         };
@@ -300,8 +299,8 @@ __device__ __forceinline__ void epilogue(const Desc& d, f32x16 (&acc)[C::R][C::N
                     if (!valid) u[e] = 0.f;
                 }
                 const int co = cf + 16 * blk + 8 * hh;
-                store8_bf16_hx<HX, C::H>(d.y, d.n, view_at(d.y, img, yy, xx, co), u);
-                if constexpr (MODE & 4) store8_bf16_hx<HX, C::H>(d.y2, d.n, view_at(d.y2, img, yy, xx, co), u);
+                store8_t<C::H>(view_at(d.y, img, yy, xx, co), u);
+                if constexpr (MODE & 4) store8_t<C::H>(view_at(d.y2, img, yy, xx, co), u);
             }
         }
     }
@@ -312,20 +311,9 @@ __device__ __forceinline__ void epilogue(const Desc& d, f32x16 (&acc)[C::R][C::N
 // XS2: the input is read as PixelShuffle(2)ᵀ (isr_conv_desc.x_sub2) — a template flag so the
 // common path carries no per-chunk address division.
 // One output tile (logical tile index t: cout tile innermost, then x, y, image) of the conv
-// described by `d`, computed by the whole workgroup.  HX = 1 (the persistent chain kernel,
-// conv_chain.hip): activations written by other workgroups of the same launch are read with
-// sc1 loads (L1 bypass) and the outputs stored write-through (sc1), Guideline 16's hand-off.
-struct NoPre {
-    __device__ void operator()() const {}
-};
-
-// pre(): run after the tile's scalar setup (descriptor loads, addresses, bias loads) is issued
-// and before its first LDS-DMA (the chain's dependency wait: the setup's memory latency then
-// overlaps the wait); with early0 the first NST-1 chunks are staged before pre() (the chain,
-// when those input channels were not written by the previous layer).
-template <class C, bool XS2, int HX, class Desc, class Pre = NoPre>
-__device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, const Pre& pre = Pre{},
-                                          bool early0 = false) {
+// described by `d`, computed by the whole workgroup.
+template <class C, bool XS2>
+__device__ __forceinline__ void conv_tile(const isr_conv_desc& d, int t) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int R = C::R, NF = C::NF, WM = C::WM;
 
@@ -348,7 +336,7 @@ __device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, c
     // same MFMA order as trunk.hip's kernel, so every path stays bit-identical.
     const bool fold = fold_ok<C, XS2>(d);
     const uint32_t fidv = C::FOLD ? fold_idv<C::H>(d.s1) : 0u;
-    conv_stamp(0, srow);
+    conv_stamp(0);
 
     // ---- per-lane glds source offsets (chunk-invariant) -------------------
     // x_sub2 (backward of PixelShuffle): halo pixel (row, col) of sub-position s
@@ -400,8 +388,7 @@ __device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, c
         for (int k = 0; k < C::IPWH; ++k) {
             const int j = wave + WM * k;
             const uint32_t o = off_of(k);
-            if constexpr (HX) glds16_sc1(xs + o, dst + j * 1024);
-            else glds16(xs + o, dst + j * 1024);
+            glds16(xs + o, dst + j * 1024);
         }
     };
     auto stage_w = [&](int chunk, int buf) {
@@ -425,8 +412,7 @@ __device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, c
             const int j = wave + WM * k;
             const uint32_t o = off_of(k);
             if (j < C::HALO_INSTR) {
-                if constexpr (HX) glds16_sc1(xs + o, dst + j * 1024);
-                else glds16(xs + o, dst + j * 1024);
+                glds16(xs + o, dst + j * 1024);
             } else if (!(C::ABL & 8) || chunk == 0) {
                 glds16(ws + o, dst + j * 1024);
             }
@@ -459,10 +445,8 @@ __device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, c
                 if (s < nchunks) stage(s, s);
         }
     };
-    if (early0) prologue();
-    pre();
-    if (!early0) prologue();
-    conv_stamp(5, srow);
+    prologue();
+    conv_stamp(5);
 
     const int qw = wave * R * C::HC + l31; // halo pixel of (row w*R, col l31)
     // one K-chunk; FC = the chunk index (0..3) when the residual fold adds its MFMAs to this chunk,
@@ -492,7 +476,7 @@ __device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, c
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            if (chunk == 0) conv_stamp(1, srow);
+            if (chunk == 0) conv_stamp(1);
             const bool refill = !(C::ABL & 2) && chunk + C::NST - 1 < nchunks;
             // split rings: w(chunk+1) then h(chunk+NST-1), each when it exists
             auto refill_split = [&]() {
@@ -655,7 +639,7 @@ __device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, c
     for (int chunk = chunk0; chunk < nchunks; ++chunk) do_chunk(chunk, IC<-1>{});
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier(); // all waves done reading the ring before it becomes the epilogue image
-    conv_stamp(2, srow);
+    conv_stamp(2);
 
     if constexpr (C::ABL & 4) {
         if (d.n < 0) { // never true: keeps the accumulators (and so the MFMAs) live
@@ -674,41 +658,33 @@ __device__ __forceinline__ void conv_tile(const Desc& d, int t, int srow = -1, c
     const int mode = d.shuffle == 2 ? (d.m.data ? 24 : 8)
                      : fold ? (32 | (d.r2.data ? 2 : 0))
                             : ((d.r1.data ? 1 : 0) | (d.r2.data ? 2 : 0) | (d.y2.data ? 4 : 0) | (d.m.data ? 16 : 0));
-    if constexpr (HX) {  // chain layers: growth (plain store) or the RDB final conv (folded r1 [+ r2])
-        if (mode == 0) epilogue<C, 0, HX>(d, acc, img, ct, x0, y0, wave, lane);
-        else if (mode == 32) epilogue<C, 32, HX>(d, acc, img, ct, x0, y0, wave, lane);
-        else if (mode == 34) epilogue<C, 34, HX>(d, acc, img, ct, x0, y0, wave, lane);
-        else if (mode == 1) epilogue<C, 1, HX>(d, acc, img, ct, x0, y0, wave, lane);
-        else epilogue<C, 3, HX>(d, acc, img, ct, x0, y0, wave, lane);
-    } else switch (mode) {
-        case 32: epilogue<C, 32, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 34: epilogue<C, 34, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 0: epilogue<C, 0, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 1: epilogue<C, 1, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 2: epilogue<C, 2, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 3: epilogue<C, 3, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 4: epilogue<C, 4, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 5: epilogue<C, 5, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 6: epilogue<C, 6, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 7: epilogue<C, 7, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 8: epilogue<C, 8, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 24: epilogue<C, 24, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 16: epilogue<C, 16, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 17: epilogue<C, 17, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        case 18: epilogue<C, 18, HX>(d, acc, img, ct, x0, y0, wave, lane); break;
-        default: epilogue<C, 19, HX>(d, acc, img, ct, x0, y0, wave, lane); break;  // 19; y2 + mask is rejected by isr_conv3x3_fwd
+    switch (mode) {
+        case 32: epilogue<C, 32>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 34: epilogue<C, 34>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 0: epilogue<C, 0>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 1: epilogue<C, 1>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 2: epilogue<C, 2>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 3: epilogue<C, 3>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 4: epilogue<C, 4>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 5: epilogue<C, 5>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 6: epilogue<C, 6>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 7: epilogue<C, 7>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 8: epilogue<C, 8>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 24: epilogue<C, 24>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 16: epilogue<C, 16>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 17: epilogue<C, 17>(d, acc, img, ct, x0, y0, wave, lane); break;
+        case 18: epilogue<C, 18>(d, acc, img, ct, x0, y0, wave, lane); break;
+        default: epilogue<C, 19>(d, acc, img, ct, x0, y0, wave, lane); break;  // 19; y2 + mask is rejected by isr_conv3x3_fwd
     }
 #ifdef ISR_TUNING
-    if (srow == -1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        conv_stamp(3, srow);
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    conv_stamp(3);
 #endif
 }
 
 template <class C, bool XS2>
 __global__ __launch_bounds__(C::NT, C::OCC) void conv3x3_fwd_kernel(isr_conv_desc d) {
-    conv_tile<C, XS2, 0>(d, xcd_remap(blockIdx.x, gridDim.x));
+    conv_tile<C, XS2>(d, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 template <class C, bool XS2>
@@ -823,268 +799,10 @@ int conv3x3_fwd_variant(const isr_conv_desc* d, int variant, hipStream_t s) {
     return -2;
 }
 
-// ============ persistent chain: a run of RDB convs in ONE launch ============
-// The RRDB trunk (utils/models.py:298-317, 245-271: per RDB four growth convs and the
-// final 192→64 conv) as one persistent launch instead of one launch per conv.  Every
-// layer shares the 16x32-pixel tile grid; workgroup b owns tiles b, b+G, ... for every
-// layer (all G workgroups resident: G <= 2 per CU, the kernel's occupancy).  Tile t of
-// layer L may start once tiles N(t) (itself and its 8 neighbours — the 3x3 halo) of layer
-// L-1 are done: their progress words reach L.  That single stencil dependency also covers
-// every older read/write hazard (a tile's layer-L-m ancestors within radius m are done).
-// Hand-off (cdna_hip_programming.md Guideline 16, R1): outputs are stored write-through
-// (sc1) and drained (s_waitcnt vmcnt(0) by every wave, barrier) before one lane publishes
-// the progress word with a relaxed agent-scope atomic store; consumers poll relaxed
-// (one lane per neighbour), then read the activations with sc1 loads (L1 bypass), and
-// with `acquire` additionally run one agent-scope acquire per tile first.
-// State (no per-call memset: a captured memset node was seen to leave garbage in the first
-// words under HIP-graph replay): state[0] = generation, bumped by a one-thread kernel ahead of
-// every chain launch; progress word of a tile = gen * 1024 + layers done (compared by serial-
-// number arithmetic, so it never needs zeroing); a bounded spin that gives up writes the
-// generation into state[1] (results invalid; the host checks state[1] == state[0]).
-struct ChainArgs {
-    const isr_conv_desc* layers;
-    const int32_t* kinds;
-    int nl, ntiles, nby, nbx;
-    unsigned* state;
-    int acquire;
-};
-
-#define CHAIN_STAMP_L0 75  // tuning stamps: the 15 layers of RRDB 5
-// chain stamp rows start past every per-conv launch's blockIdx rows (those stamp at row
-// blockIdx.x: up to 8192 for the x4 Scaler), so the later launches of a forward cannot
-// overwrite them
-#define CHAIN_STAMP_BASE 65536
-
-#ifdef ISR_TUNING
-// isr_tuning_chain_knobs: [0] start delay (s_memrealtime ticks, 100 MHz) of the workgroups whose
-// bit [1] of blockIdx.x is set (a phase offset between independent image groups)
-__device__ int g_chain_knobs[4];
-#endif
-
-__device__ __forceinline__ void chain_tuning_prologue(int ntiles) {
-#ifdef ISR_TUNING
-    unsigned long long* p = g_conv_stamps;
-    if (p != nullptr && threadIdx.x == 0) {  // placement of every workgroup, after the 15 stamped layers
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);   // HW_REG_HW_ID
-        const unsigned xcc = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 20); // HW_REG_XCC_ID
-        p[((size_t)CHAIN_STAMP_BASE + 15 * ntiles + blockIdx.x) * 8 + 6] = hw;
-        p[((size_t)CHAIN_STAMP_BASE + 15 * ntiles + blockIdx.x) * 8 + 7] = xcc;
-    }
-    const int dly = g_chain_knobs[0];
-    if (dly > 0 && ((blockIdx.x >> g_chain_knobs[1]) & 1)) {
-        unsigned long long t0, t;
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
-        do {
-            __builtin_amdgcn_s_sleep(8);
-            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        } while (t - t0 < (unsigned long long)dly);
-    }
-#else
-    (void)ntiles;
-#endif
-}
-
-// The round-2 per-tile chain kernel (isr_conv_chain variant 1): superseded by trunk.hip, kept in the
-// tuning library only (-DISR_TUNING).
-#ifdef ISR_TUNING
-__global__ void chain_bump_kernel(unsigned* state) {
-    if (threadIdx.x == 0) state[threadIdx.x] = state[threadIdx.x] + 1u;  // vector store by lane 0
-}
-
-__device__ __forceinline__ void chain_wait(const ChainArgs& a, int t, unsigned need, unsigned gen) {
-    unsigned* progress = a.state + 4;
-    if (wave_id() == 0) {
-        const int lane = threadIdx.x & 63;
-        int nb = -1;
-        if (lane < 9) {
-            const int bx = t % a.nbx, by = (t / a.nbx) % a.nby, img = t / (a.nbx * a.nby);
-            const int yy = by + lane / 3 - 1, xx = bx + lane % 3 - 1;
-            if (yy >= 0 && yy < a.nby && xx >= 0 && xx < a.nbx) nb = (img * a.nby + yy) * a.nbx + xx;
-        }
-        for (unsigned spins = 0;; ++spins) {
-            const bool ok =
-                nb < 0 ||
-                (int)(__hip_atomic_load(progress + nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - need) >= 0;
-            if (__all(ok)) break;
-            // a neighbour never arrived (not resident?): give up after ~0.3 s, flag it, and let
-            // every later wait of the launch give up at once, so the grid always drains
-            if ((spins & 255) == 255 &&
-                __hip_atomic_load(a.state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen)
-                break;
-            if (spins > (1u << 18)) {
-                if (lane == 0) {
-                    __hip_atomic_store(a.state + 1, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_fetch_add(a.state + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (a.acquire) {
-            if (lane == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-}
-
-typedef const __attribute__((address_space(4))) isr_conv_desc const_desc;  // constant memory:
-// the host writes the layer table before the launch, so the compiler may re-load any field
-// (s_load) instead of holding it in registers across the tile
-
-// Static assignment: workgroup b owns tiles b, b+G, ... for every layer, so a tile's own
-// previous-layer outputs were written by the same CU.  A queue dealing (layer, tile) items in
-// layer order (no residency assumption) measured slower: 9.3 vs 6.8 ms per forward — it
-// rebuilds a per-layer front and loses that locality.  All G workgroups must be resident
-// (G <= 2 per CU); a wait that never completes gives up (bounded) instead of hanging.
-// WM_: 0 = dependency wait before the tile; 1 = inside conv_tile after its scalar setup (the
-// descriptor loads overlap the wait); 2 = as 1, and the first chunk is staged before the wait
-// when the previous layer did not write those input channels (every layer but an RDB's first);
-// 3 = as 1, and a tile's store drain + progress publish is deferred into the NEXT tile's pre(),
-// after that tile's scalar setup (the write-through drain overlaps the setup's latency)
-template <class CG, class CF, int WM_ = 0>
-__global__ __launch_bounds__(CG::NT, 2) void conv_chain_kernel(ChainArgs a) {
-    // bumped by chain_bump_kernel before this launch; an agent-scope load, so no CU reads a
-    // stale copy of another XCD's write
-    const unsigned gen = __hip_atomic_load(a.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    chain_tuning_prologue(a.ntiles);
-    int pend_t = -1;  // WM_ 3: tile whose stores are not yet drained / published (uniform)
-    unsigned pend_v = 0;
-    auto publish_pending = [&]() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its sc1 stores are done
-        __syncthreads();
-        if (threadIdx.x == 0)
-            __hip_atomic_store(a.state + 4 + pend_t, pend_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        pend_t = -1;
-    };
-    for (int L = 0; L < a.nl; ++L) {
-        const_desc& d = ((const_desc*)(uintptr_t)a.layers)[L];
-        const int kind = a.kinds[L];
-        for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-#ifdef ISR_TUNING
-            const int srow =
-                (L >= CHAIN_STAMP_L0 && L < CHAIN_STAMP_L0 + 15) ? CHAIN_STAMP_BASE + (L - CHAIN_STAMP_L0) * a.ntiles + t : -2;
-#else
-            const int srow = -2;
-#endif
-            conv_stamp(4, srow);  // wait start
-            if constexpr (WM_ == 0) {
-                if (L > 0) chain_wait(a, t, gen * 1024u + (unsigned)L, gen);
-                if (kind == 0) conv_tile<CG, false, 1>(d, t, srow);
-                else conv_tile<CF, false, 1>(d, t, srow);
-            } else {
-                bool early0 = false;
-                if (WM_ == 2 && L > 0) {
-                    // first-chunk input channels [x.coff, x.coff + 16) vs the previous layer's output
-                    const_desc& dp = ((const_desc*)(uintptr_t)a.layers)[L - 1];
-                    const int ech = 16 * (kind == 0 ? CG::NST - 1 : CF::NST - 1);  // channels staged early
-                    early0 = !(dp.y.data == d.x.data && dp.y.coff < d.x.coff + ech && d.x.coff < dp.y.coff + dp.cout);
-                }
-                auto pre = [&]() {
-                    if (WM_ == 3 && pend_t >= 0) publish_pending();
-                    if (L > 0) chain_wait(a, t, gen * 1024u + (unsigned)L, gen);
-                };
-                if (kind == 0) conv_tile<CG, false, 1>(d, t, srow, pre, early0);
-                else conv_tile<CF, false, 1>(d, t, srow, pre, early0);
-                if constexpr (WM_ == 3) {
-                    pend_t = t;
-                    pend_v = gen * 1024u + (unsigned)(L + 1);
-                    continue;
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its sc1 stores are done
-            conv_stamp(3, srow);
-            __syncthreads();
-            if (threadIdx.x == 0)
-                __hip_atomic_store(a.state + 4 + t, gen * 1024u + (unsigned)(L + 1), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (pend_t >= 0) publish_pending();
-}
-
-
-#ifdef ISR_TUNING
-static int g_chain_variant_host = 0;  // isr_tuning_chain_knobs k2: chain kernel variant (A/B only)
-#endif
-
-template <class CG, class CF, int WM_ = 0>
-static int launch_chain(const isr_chain_desc* c, hipStream_t s) {
-    static_assert(CG::TH == CF::TH && CG::TW == CF::TW, "one tile grid");
-    static_assert(CG::NT == CF::NT, "one block size");
-    if (c->ha % CG::TH || c->wa % CG::TW) return -2;
-    ChainArgs a;
-    a.layers = c->layers;
-    a.kinds = c->kinds;
-    a.nl = c->nl;
-    a.nby = c->ha / CG::TH;
-    a.nbx = c->wa / CG::TW;
-    a.ntiles = c->n * a.nby * a.nbx;
-    a.state = c->state;
-    a.acquire = c->acquire;
-    if (c->nl >= 1024) return -2;
-    hipLaunchKernelGGL(chain_bump_kernel, dim3(1), dim3(64), 0, s, c->state);
-    auto kern = conv_chain_kernel<CG, CF, WM_>;
-    constexpr int lds = CG::LDS > CF::LDS ? CG::LDS : CF::LDS;
-    lds_limit((const void*)kern, lds);
-    int per_cu = 0;  // residency from the occupancy API (registers, LDS), capped at the 2 it is built for
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, CG::NT, lds) != hipSuccess) return -1;
-    per_cu = per_cu < 2 ? per_cu : 2;
-    if (per_cu < 1) return -1;
-    const int slots = per_cu * cu_count();  // every workgroup resident
-    const int grid = a.ntiles < slots ? a.ntiles : slots;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(CG::NT), lds, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int conv_chain(const isr_chain_desc* c, hipStream_t s) {
-#ifdef ISR_TUNING
-    switch (g_chain_variant_host) {
-        case 1:  // RDB final conv: every residual unit of a pass loaded at once (EPQ 8)
-            return launch_chain<V_G0, C3<4, 4, 2, 16, 2, 192, 0, 2, 8>>(c, s);
-        case 2:  // 32x32 tiles, 8 waves, 1 block / CU: growth 3-deep ring, final 2-deep
-            return launch_chain<C3<4, 8, 1, 16, 3, 0, 0, 2>, C3<4, 8, 2, 16, 2, 192, 0, 2>>(c, s);
-        case 3:  // 2 + EPQ 8
-            return launch_chain<C3<4, 8, 1, 16, 3, 0, 0, 2>, C3<4, 8, 2, 16, 2, 192, 0, 2, 8>>(c, s);
-        case 4:  // 32x32 tiles, both 2-deep
-            return launch_chain<C3<4, 8, 1, 16, 2, 0, 0, 2>, C3<4, 8, 2, 16, 2, 192, 0, 2>>(c, s);
-        case 9:  // deferred drain + publish (WM 3)
-            return launch_chain<V_G0, V_F0, 3>(c, s);
-        case 7:  // growth convs: split rings (halo 3 deep, weights 2 deep), wait after setup
-            return launch_chain<C3<4, 4, 1, 16, 3, 0, 0, 2, 4, 0, 0, 2>, V_F0, 1>(c, s);
-        case 8:  // 7 with the wait before the tile
-            return launch_chain<C3<4, 4, 1, 16, 3, 0, 0, 2, 4, 0, 0, 2>, V_F0, 0>(c, s);
-        case 5:  // the wait before the tile (the round-2 form; production waits after the setup)
-            return launch_chain<V_G0, V_F0, 0>(c, s);
-        case 6:  // 5 + first chunk staged before the wait where independent of the previous layer
-            return launch_chain<V_G0, V_F0, 2>(c, s);
-        default: break;
-    }
-#endif
-    // production: the dependency wait runs after the tile's scalar setup (its descriptor loads —
-    // three dependent scalar round trips, ~2.4 µs per tile — overlap the wait): -1.2 % per
-    // forward against waiting first (tools/chain_probe.py, variant 0 vs 5)
-    return launch_chain<V_G0, V_F0F, 1>(c, s);
-}
-
-#else
-int conv_chain(const isr_chain_desc*, hipStream_t) { return -3; }
-#endif  // ISR_TUNING (round-2 chain)
-
-size_t conv_chain_state_words(int n, int ha, int wa) {
-    const size_t tiles = (size_t)n * (ha / V_G0::TH) * (wa / V_G0::TW);
-    return (tiles + 4 + 3) / 4 * 4;  // [0] fail word, [4..] progress; a multiple of 16 bytes
-}
-
 #ifdef ISR_TUNING
 int conv_stamps_set(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_conv_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -1; }
-int chain_knobs_set(const int* k) {
-    g_chain_variant_host = k[2];
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_chain_knobs), k, 4 * sizeof(int)) == hipSuccess ? 0 : -1;
-}
 #else
 int conv_stamps_set(void*) { return -2; }
-int chain_knobs_set(const int*) { return -2; }
 #endif
 
 int conv3x3_fwd_dispatch(const isr_conv_desc* d, hipStream_t s) {

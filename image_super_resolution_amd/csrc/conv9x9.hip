@@ -159,134 +159,21 @@ __global__ void pack_head_kernel(const float* __restrict__ w, OT* __restrict__ o
 }
 
 // ============================== tail ======================================
-namespace tail {
-constexpr int TH = 16, TW = 32, WM = 4;
-constexpr int TR = TH + 8;        // T rows (input rows of the tile)
-constexpr int RT = TR / WM;       // T rows per wave (6)
-constexpr int HC = TW + 8;        // 40 halo cols
-constexpr int HIPL = TR * HC / 32;           // 30 glds per 16-channel plane (32 px x 32 B)
-constexpr int HALO_INSTR = 2 * HIPL;          // 60 per 32-channel chunk
-constexpr int HALO_BYTES = HALO_INSTR * 1024; // 61440
-constexpr int W_BYTES = 9 * 2 * 2 * 32 * 32;  // [kx][chunk][ks][n][hpos][8] bf16 = 36864
-constexpr int W_INSTR = W_BYTES / 1024;       // 36
-constexpr int TS = 33;                        // floats per pixel in the T image (conflict-free column sums)
-constexpr int T_BYTES = TR * 32 * TS * 4;     // 101376
-constexpr int P1 = 2 * HALO_BYTES + W_BYTES;  // 159744: both chunks resident, loaded up front
-constexpr int LDS = P1 > T_BYTES ? P1 : T_BYTES;
-constexpr int HALO_PER_WAVE = HALO_INSTR / WM;  // 15 glds per wave per chunk
-static_assert(HALO_INSTR % WM == 0 && W_INSTR % WM == 0, "even glds split keeps vmcnt counting exact");
-static_assert(TR * HC % 32 == 0, "");
-}  // namespace tail
-
+// Two kernels ship: the 8-wave row-streaming walk (variant 5, production) and the 8-row per-tile
+// kernel (variant 3, the fallback of images whose output passes 2 GiB).  Both give the same bits:
+// the same MFMA order per T element and the same ky-sum order.  The forms that lost their A/B (the
+// 16-row per-tile kernel, the persistent, 4-wave and lane-streaming walks) were removed; their
+// measurements are in DESIGN.md section 5.
 // packed tail weights: [kx 9][chunk 2][ks 2][n 32][hpos 2][8] bf16,
 // n = ky*3 + co (27 used), element = W[co][chunk*32 + ks*16 + h*8 + e][ky][kx], h = hpos ^ ((n>>3)&1).
-#ifdef ISR_TUNING  // variant 1 (the 16-row per-tile kernel): tuning library only
-__global__ __launch_bounds__(256) void tail9x9_kernel(isr_tail_desc d) {
-    using namespace tail;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int img = blockIdx.z;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
-    const int wave = wave_id();
-    const int lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
+namespace tail {
+constexpr int W_BYTES = 9 * 2 * 2 * 32 * 32;  // [kx][chunk][ks][n][hpos][8] bf16 = 36864
+}  // namespace tail
 
-    const char* xbase = view_at(d.x, img, y0 - 4, x0 - 4, 0);
-    const size_t pstride = plane_bytes(d.x);
-    const int xrow = d.x.wp * 32;
-    char* wl = smem + 2 * HALO_BYTES;
-
-    f32x16 acc[RT];
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[t][g] = 0.f;
-
-    // Issue every load of the tile at once (weights, chunk-0 halo, chunk-1 halo) so the
-    // chunk-1 fetch overlaps the chunk-0 MFMAs.  Halo image per chunk: [plane kp][pixel q][2 units].
-    for (int j = wave; j < W_INSTR; j += WM)
-        glds16((const char*)d.wpack + j * 1024 + lane * 16, wl + j * 1024);
-#pragma unroll
-    for (int chunk = 0; chunk < 2; ++chunk)
-        for (int j = wave; j < HALO_INSTR; j += WM) {
-            const int kp = j / HIPL;
-            const int u = (j - kp * HIPL) * 64 + lane;
-            const int q = u >> 1;
-            const int row = q / HC, col = q - row * HC;
-            const int c = (u & 1) ^ ((q >> 3) & 1);
-            glds16(xbase + (size_t)(chunk * 2 + kp) * pstride + row * xrow + col * 32 + c * 16,
-                   smem + chunk * HALO_BYTES + j * 1024);
-        }
-
-#pragma unroll
-    for (int chunk = 0; chunk < 2; ++chunk) {
-        if (chunk == 0)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HALO_PER_WAVE) : "memory");
-        else
-            wait_vm0();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const char* halo = smem + chunk * HALO_BYTES;
-#pragma unroll
-        for (int kx = 0; kx < 9; ++kx) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int n = l31;
-                const bf16x8 b = lds_read16(wl + ((((kx * 2 + chunk) * 2 + ks) * 32 + n) * 2 + (hh ^ ((n >> 3) & 1))) * 16);
-                const char* hp = halo + ks * HIPL * 1024;
-#pragma unroll
-                for (int t = 0; t < RT; ++t) {
-                    const int q = (wave * RT + t) * HC + kx + l31;
-                    acc[t] = mfma32(lds_read16(hp + halo_unit2(q, hh) * 16), b, acc[t]);
-                }
-            }
-        }
-    }
-    __syncthreads();
-
-    float* T = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const int px = (g & 3) + 8 * (g >> 2) + 4 * hh;
-            T[((wave * RT + t) * 32 + px) * TS + l31] = acc[t][g];
-        }
-    __syncthreads();
-
-    const size_t plane = (size_t)d.h * d.w;
-    for (int item = threadIdx.x; item < TH * TW; item += 256) {
-        const int yr = item >> 5, px = item & 31;
-        const int yy = y0 + yr, xx = x0 + px;
-        float s[3];
-#pragma unroll
-        for (int co = 0; co < 3; ++co) s[co] = d.bias ? d.bias[co] : 0.f;
-#pragma unroll
-        for (int ky = 0; ky < 9; ++ky) {
-            const float* tp = T + ((yr + ky) * 32 + px) * TS + ky * 3;
-#pragma unroll
-            for (int co = 0; co < 3; ++co) s[co] += tp[co];
-        }
-        if (yy < d.h && xx < d.w) {
-            const size_t o = (size_t)img * 3 * plane + (size_t)yy * d.w + xx;
-#pragma unroll
-            for (int co = 0; co < 3; ++co) {
-                const float t = tanhf(s[co]);
-                if (d.y_u8) {
-                    const float q = rintf((t + 1.f) / 2.f * 255.f);
-                    ((uint8_t*)d.y)[o + co * plane] = (uint8_t)fminf(fmaxf(q, 0.f), 255.f);
-                } else {
-                    ((float*)d.y)[o + co * plane] = t;
-                }
-            }
-        }
-    }
-}
-
-#endif
-
-// ---- 8-row tail (variant 3): the per-tile kernel with 8 output rows per block and one
+// ---- 8-row tail (variant 3): a per-tile kernel with 8 output rows per block and one
 // 32-channel halo chunk resident at a time (chunk 1 refills chunk 0's slot after a
 // barrier), so LDS is 76 KB and two blocks share a CU: one block's halo fetch runs
-// beside the other's MFMAs.  Same MFMA order and ky-sum order as tail9x9_kernel.
+// beside the other's MFMAs.
 namespace tail8 {
 constexpr int TH = 8, TW = 32, WM = 4;
 constexpr int TR = TH + 8;                    // 16 input rows
@@ -406,247 +293,11 @@ __global__ __launch_bounds__(256, 2) void tail9x9_k8_kernel(isr_tail_desc d) {
     }
 }
 
-// ---- persistent tail (variant 2, not production: see tail9x9_fwd_variant): one block per CU walks its tiles, 16-channel halo planes
-// stream through a 3-deep LDS ring (the next tile's first planes load while this
-// tile finishes), weights stay resident, and the ky-sum goes through small per-wave
-// partial-sum slices instead of a full T image.  Deterministic: each slice is
-// written by one wave in program order, the slices are added in a fixed order.
-namespace tailp {
-using tail::TH; using tail::TW; using tail::WM; using tail::TR; using tail::RT; using tail::HC; using tail::HIPL;
-constexpr int NST = 3;
-constexpr int GPW = 8;                          // glds per wave per plane (30 used + 2 dummy over 4 waves)
-constexpr int SLOT = GPW * WM * 1024;           // 32 KB
-constexpr int W_BYTES = tail::W_BYTES;          // 36 KB, 9 glds per wave
-constexpr int OS = 131;                         // floats per slice row (≡ 3 mod 64: the 27 (ky, co) lanes hit 27 banks)
-__host__ __device__ constexpr int lo(int w) { return 6 * w - 8 > 0 ? 6 * w - 8 : 0; }
-__host__ __device__ constexpr int hi(int w) { return 6 * w + 5 < TH - 1 ? 6 * w + 5 : TH - 1; }
-__host__ __device__ constexpr int rows_before(int w) { return w == 0 ? 0 : rows_before(w - 1) + hi(w - 1) - lo(w - 1) + 1; }
-constexpr int SLICE_ROWS = rows_before(WM);
-constexpr int SLICE_BYTES = SLICE_ROWS * OS * 4;
-constexpr int LDS = W_BYTES + NST * SLOT + SLICE_BYTES;
-static_assert(LDS <= 163840, "LDS budget");
-static_assert(HIPL <= GPW * WM && tail::W_INSTR % WM == 0, "");
-static_assert(RT * WM == TR && TH * TW % 256 == 0, "");
-}  // namespace tailp
-
-// ABL (timing probes, outputs wrong): 2 = no MFMAs, 4 = no epilogue (slices / stores),
-// 8 = slices but no reduce / store
-template <int ABL = 0>
-__global__ __launch_bounds__(256, 1) void tail9x9_pkernel(isr_tail_desc d, int ntiles) {
-    using namespace tailp;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* wl = smem;
-    char* ring = smem + W_BYTES;
-    float* slices = reinterpret_cast<float*>(smem + W_BYTES + NST * SLOT);
-    const int wave = wave_id();
-    const int lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
-    const int G = gridDim.x;
-    const int b = xcd_remap(blockIdx.x, G);
-    const int mine = b < ntiles ? (ntiles - b + G - 1) / G : 0;
-    const int nch = mine * 4;
-    const int nbx = d.wa / TW, nby = d.ha / TH;
-    const size_t pstride = plane_bytes(d.x);
-    const int xrow = d.x.wp * 32;
-
-    for (int j = wave; j < tail::W_INSTR; j += WM)
-        glds16((const char*)d.wpack + j * 1024 + lane * 16, wl + j * 1024);
-    for (int i = threadIdx.x; i < SLICE_ROWS * OS; i += 256) slices[i] = 0.f;
-
-    uint32_t off[GPW];
-#pragma unroll
-    for (int k = 0; k < GPW; ++k) {
-        const int j = wave + WM * k;
-        uint32_t o = 0;  // j >= HIPL: dummy copy into the slot's unused tail
-        if (j < HIPL) {
-            const int u = j * 64 + lane;
-            const int q = u >> 1;
-            const int row = q / HC, col = q - row * HC;
-            const int c = (u & 1) ^ ((q >> 3) & 1);
-            o = (uint32_t)(row * xrow + col * 32 + c * 16);
-        }
-        off[k] = o;
-    }
-    auto tile_of = [&](int g, int& img, int& y0, int& x0) {
-        int t = b + (g >> 2) * G;
-        x0 = (t % nbx) * TW; t /= nbx;
-        y0 = (t % nby) * TH;
-        img = t / nby;
-    };
-    auto issue = [&](int g) {
-        int img, y0, x0;
-        tile_of(g, img, y0, x0);
-        const char* base = view_at(d.x, img, y0 - 4, x0 - 4, 0) + (size_t)(g & 3) * pstride;
-        char* dst = ring + (g % NST) * SLOT;
-#pragma unroll
-        for (int k = 0; k < GPW; ++k) glds16(base + off[k], dst + (wave + WM * k) * 1024);
-    };
-    if (nch > 0) issue(0);
-    if (nch > 1) issue(1);
-
-    f32x16 acc[RT];
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[t][g] = 0.f;
-    const int n = l31, ky = n / 3, co = n - 3 * (n / 3);
-    float* myslice = slices + rows_before(wave) * OS;  // wave-uniform
-    const int mylo = lo(wave), myhi = hi(wave);
-
-    // reduce the 4 wave slices of the tile ending at chunk g (fixed order: deterministic),
-    // zero them for the next tile, bias + tanh (+ uint8), store NCHW
-    auto finish = [&](int g) {
-        if constexpr (ABL & 8) return;
-        int img, y0, x0;
-        tile_of(g, img, y0, x0);
-        const size_t plane = (size_t)d.h * d.w;
-#pragma unroll
-        for (int k = 0; k < 3 * TH * TW / 256; ++k) {
-            const int it = threadIdx.x + 256 * k;
-            const int oc = it / (TH * TW), rem = it - oc * (TH * TW);
-            const int y = rem / TW, px = rem - y * TW;
-            float s = d.bias ? d.bias[oc] : 0.f;
-#pragma unroll
-            for (int w = 0; w < WM; ++w) {
-                if (y >= lo(w) && y <= hi(w)) {
-                    float* p = slices + (rows_before(w) + y - lo(w)) * OS + px * 3 + oc;
-                    s += *p;
-                    *p = 0.f;
-                }
-            }
-            const int yy = y0 + y, xx = x0 + px;
-            if (yy < d.h && xx < d.w) {
-                const size_t o = (size_t)img * 3 * plane + (size_t)oc * plane + (size_t)yy * d.w + xx;
-                const float th = tanhf(s);
-                if (d.y_u8) {
-                    const float q = rintf((th + 1.f) / 2.f * 255.f);
-                    ((uint8_t*)d.y)[o] = (uint8_t)fminf(fmaxf(q, 0.f), 255.f);
-                } else {
-                    ((float*)d.y)[o] = th;
-                }
-            }
-        }
-    };
-
-    for (int g = 0; g < nch; ++g) {
-        if (g + 1 < nch) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GPW) : "memory");
-        } else {
-            wait_vm0();
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (!(ABL & 4) && g > 0 && (g & 3) == 0) {
-            finish(g - 1);  // slices complete: every wave passed this barrier after writing them
-            // the slices are re-zeroed here and next written after 3 more chunk barriers
-        }
-        if (g + 2 < nch) issue(g + 2);
-
-        const char* hs = ring + (g % NST) * SLOT;
-        const int c16 = g & 3, chunk = c16 >> 1, ks = c16 & 1;
-        bf16x8 fb[2], fa[2][RT];
-        auto rd = [&](int kx, int idx, int set) {
-            if (idx == 0) {
-                fb[set] = lds_read16(wl + ((((kx * 2 + chunk) * 2 + ks) * 32 + n) * 2 + (hh ^ ((n >> 3) & 1))) * 16);
-            } else {
-                const int t = idx - 1;
-                fa[set][t] = lds_read16(hs + halo_unit2((wave * RT + t) * HC + kx + l31, hh) * 16);
-            }
-        };
-#pragma unroll
-        for (int i = 0; i <= RT; ++i) rd(0, i, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int kx = 0; kx < 9; ++kx) {
-            const int cur = kx & 1;
-#pragma unroll
-            for (int t = 0; t < RT; ++t) {
-                if constexpr (ABL & 2) {
-                    asm volatile("" ::"v"(fa[cur][t]), "v"(fb[cur]));
-                } else {
-                    acc[t] = mfma32(fa[cur][t], fb[cur], acc[t]);
-                }
-                if (kx + 1 < 9)
-                    for (int i = t * (RT + 1) / RT; i < (t + 1) * (RT + 1) / RT; ++i) rd(kx + 1, i, cur ^ 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-
-        if (c16 == 3 && !(ABL & 4)) {  // tile done: partial ky-sums → this wave's slice
-            // read-modify-write in program order (LDS is in order per wave; within one
-            // instruction the 27 (ky, co) lanes hit distinct rows, so no atomics are needed)
-#pragma unroll
-            for (int t = 0; t < RT; ++t) {
-                const int y = wave * RT + t - ky;
-                const bool ok = n < 27 && y >= mylo && y <= myhi;
-                float* row = myslice + (y - mylo) * OS + co;
-                float v[16];
-#pragma unroll
-                for (int gg = 0; gg < 16; ++gg) {
-                    const int px = (gg & 3) + 8 * (gg >> 2) + 4 * hh;
-                    v[gg] = ok ? row[px * 3] : 0.f;
-                }
-#pragma unroll
-                for (int gg = 0; gg < 16; ++gg) {
-                    const int px = (gg & 3) + 8 * (gg >> 2) + 4 * hh;
-                    if (ok) row[px * 3] = v[gg] + acc[t][gg];
-                    acc[t][gg] = 0.f;
-                }
-            }
-        }
-    }
-    // the last tile's reduce + store (earlier tiles' run at the top of the next tile's
-    // first chunk, before that chunk's refill is issued, so the refill stays the youngest
-    // vmcnt group and the next wait stays exact)
-    if (nch > 0 && !(ABL & 4)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        finish(nch - 1);
-    }
-}
-
-// ---- row-streaming tail (variant 4): no recomputed rows.  A block owns a 32-column strip of
-// one image over `sh` output rows and walks DOWN it: each wave turns one input row into its
-// T row (the 1x9 row conv, N = (ky, co)) with 36 MFMAs, every T row is computed once (the
-// per-tile kernels recompute the 8 halo rows of every tile: 2x the MFMA work at 8-row tiles),
-// and output row y is finished once T rows y-4 .. y+4 exist.  Input rows stream through a
-// 3-group LDS ring (4 rows per group, two groups in flight); the T terms go to a 16-row ring
-// keyed by the output row they feed (O[r0][px][pos(co, ky)] = T(r0+ky)[px][ky*3+co]).
-// The 36 weight fragments stay in VGPRs (one LDS read per MFMA instead of two: with weights
-// in LDS the four waves' fragment reads saturated the LDS port before the MFMAs did).  One
-// wave per SIMD, so the finish of an older output row (T reads, ky sums, tanh, 2 stores) is
-// interleaved into the MFMA sequence of the current T row.  Same MFMA order per T element and
-// the same ky-sum order as the per-tile kernels: bit-identical outputs.
-// LDS reads of the loop are asm (lds_read16_async / lds_read16f4_async) with counted lgkmcnt
-// waits: hipcc's own waits here were lgkmcnt(0) every few MFMAs.  Counted vmcnt: per wave,
-// 5 LDS-DMA per row group and exactly 2 stores per finished row.
-namespace tails {
-constexpr int TW = 32, WM = 4, GR = 4;       // strip width, waves, rows per group (one per wave)
-constexpr int HC = TW + 8;                    // 40 input columns per row
-constexpr int ROWB = 4 * HC * 32;             // one input row image: 4 planes x 40 px x 32 B = 5120
-constexpr int ROW_INSTR = ROWB / 1024;        // 5
-constexpr int NG = 3;                         // input row groups in the ring
-constexpr int NT = 16;                        // O ring rows: read 4i-16 .. 4i-13 while writing 4i-12 .. 4i-1
-constexpr int TS = 36;                        // O row: [px][co 0: 0..8, co 1: 9..17, co 2: 20..28] + pad
-constexpr int TROW = TW * TS * 4;             // 4608 (TS = 36: conflict-free 16-B px reads)
-constexpr int OFF_IN = 0;
-constexpr int OFF_T = OFF_IN + NG * GR * ROWB;      // 61440
-constexpr int LDS = OFF_T + NT * TROW;             // 135168
-constexpr int PD = 6;                          // A-fragment prefetch distance (MFMA steps)
-constexpr int ST = 2;                          // stores per finished row per wave
-static_assert(LDS <= 163840, "LDS");
-}  // namespace tails
-
 __device__ __forceinline__ f32x4 lds_read16f4_async(const char* p) {
     f32x4 r;
     const uint32_t a = (uint32_t)(uintptr_t)ISR_LDS_PTR(p);
     asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(a) : "memory");
     return r;
-}
-template <int N>
-__device__ __forceinline__ void lds_wait_t(bf16x8& a, f32x4 (&t)[5]) {
-    asm volatile("s_waitcnt lgkmcnt(%6)"
-                 : "+v"(a), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4])
-                 : "i"(N));
 }
 template <int N>
 __device__ __forceinline__ void lds_wait_t4(f32x4 (&t)[5]) {
@@ -658,250 +309,31 @@ template <int N>
 __device__ __forceinline__ void lds_wait1(bf16x8& a) {
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "i"(N));
 }
-__device__ __forceinline__ void vm_wait(int n) {  // s_waitcnt vmcnt(n), n a small runtime-uniform value
+__device__ __forceinline__ void vm_wait(int n) {  // s_waitcnt vmcnt(n), n = 0 or 2 (runtime-uniform)
     switch (n) {
         case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
         case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
         default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
     }
 }
 
-#ifdef ISR_TUNING
-__device__ unsigned long long* g_tail_stamps;  // isr_tuning_tail_stamps
-#endif
-__device__ __forceinline__ unsigned long long rt_now() {
-    unsigned long long t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-
-// ABL (tuning builds only, outputs wrong): 1 no MFMA, 2 no output-row finish, 4 no row DMA in the
-// loop; 16 (outputs right) per-wave s_memrealtime sums: [entry, exit, top wait + barrier, loop]
-//
-// Schedule of iteration i (wave w), one wave per SIMD so every side job rides in the gaps of
-// the 36-MFMA chain of T row 4i+w (one A-fragment read per gap, PD steps ahead):
-//   gaps 1..5    LDS-DMA of row group i+2 (one 1-KB copy per gap)
-//   gaps 6..21   O-ring writes of T row 4(i-1)+w (the previous iteration's accumulator)
-//   gaps 1..9    ky sums of output row 4(i-4)+w (its O-ring terms read before the prefetch)
-//   gaps 12, 24  tanh + store of its two channel slots
-// so a T row is written one iteration after it is computed and read one iteration later.
-template <int ABL, int PD = tails::PD>
-__global__ __launch_bounds__(256, 1) void tail9x9_stream_kernel(isr_tail_desc d, int sh) {
-    using namespace tails;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int nstrip = d.wa / TW, nseg = d.ha / sh;
-    int b = xcd_remap(blockIdx.x, gridDim.x);  // neighbouring strips (shared halo columns) on one XCD
-    const int strip = b % nstrip;
-    b /= nstrip;
-    const int seg = b % nseg;
-    const int img = b / nseg;
-    const int x0 = strip * TW, ys = seg * sh;
-    const int wave = wave_id();
-    const int lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
-    const int nit = sh / GR + 2;  // T rows ys-4 .. ys+sh+3, four per iteration
-    float* T = reinterpret_cast<float*>(smem + OFF_T);
-    const size_t pstride = plane_bytes(d.x);
-    const char* xcol = view_at(d.x, img, 0, x0 - 4, 0);  // row 0 of the strip's input columns
-    const int xrow = d.x.wp * 32;
-
-    // LDS-DMA of row group g (T rows ys-4+4g .. +3) into ring slot g % NG: wave w moves row w,
-    // 16-byte unit u = j*64 + lane of the row image from source offset doff[j]
-    uint32_t doff[ROW_INSTR];
-#pragma unroll
-    for (int j = 0; j < ROW_INSTR; ++j) {
-        const int u = j * 64 + lane;
-        const int p = u / (2 * HC), r = u - p * 2 * HC;
-        const int q = r >> 1, c = (r & 1) ^ ((q >> 3) & 1);
-        doff[j] = (uint32_t)(p << 16 | (q * 32 + c * 16));  // plane (pstride may exceed 4 GB) | in-plane
-    }
-    auto dma = [&](int g, int j) {
-        const int y = ys - 4 + GR * g + wave;  // within the buffer's zero border (pad 4)
-        glds16(xcol + (ptrdiff_t)y * xrow + (size_t)(doff[j] >> 16) * pstride + (doff[j] & 0xffff),
-               smem + OFF_IN + ((g % NG) * GR + wave) * ROWB + j * 1024);
-    };
-    // the B fragments of the 36 k-steps (chunk, kx, ks), resident for the whole strip
-    bf16x8 wr[36];
-#pragma unroll
-    for (int st = 0; st < 36; ++st) {
-        const int chunk = st / 18, kx = (st / 2) % 9, ks = st & 1, n = l31;
-        wr[st] = *reinterpret_cast<const bf16x8*>((const char*)d.wpack +
-                                                  ((((kx * 2 + chunk) * 2 + ks) * 32 + n) * 2 + (hh ^ ((n >> 3) & 1))) * 16);
-    }
-#pragma unroll
-    for (int j = 0; j < ROW_INSTR; ++j) dma(0, j);
-    if (nit > 1) {
-#pragma unroll
-        for (int j = 0; j < ROW_INSTR; ++j) dma(1, j);
-    }
-    unsigned long long t_entry = 0, t_wait = 0, t_loop = 0, t_a = 0;
-    if constexpr (ABL & 16) t_entry = rt_now();
-
-    const size_t plane = (size_t)d.h * d.w;
-    const int esz = d.y_u8 ? 1 : 4;
-    // unconditional buffer stores (lanes off the image get an offset past num_records and are
-    // dropped) so that every wave issues exactly ST stores per row
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)d.y + (size_t)img * 3 * plane * esz, (short)0, (int)(3 * plane * esz), 0x00020000);
-    // lanes 0..31 finish channels 0 and 1 of pixel l31, lanes 32..63 channel 2
-    const int cA = hh ? 2 : 0;
-    const float biasA = d.bias ? d.bias[cA] : 0.f, biasB = d.bias ? d.bias[1] : 0.f;
-    // O-ring slot of this lane's T column n = l31 = ky*3+co: row (T row - ky), position pos;
-    // n = 27..31 (padding columns of the MFMA) land in unread pad floats 29..33
-    const int wky = l31 < 27 ? l31 / 3 : 9;
-    const int wco = l31 - 3 * (l31 / 3);
-    const int wpos = l31 < 27 ? (wco == 0 ? wky : wco == 1 ? 9 + wky : 20 + wky) : 29 + (l31 - 27);
-    f32x16 accp;  // T row of the previous iteration, written into the O ring during this one
-
-    for (int i = 0; i <= nit + 1; ++i) {
-        const bool fin_prev2 = i - 2 >= 4, fin_prev1 = i - 1 >= 4;
-        // group i landed.  Younger VMEM ops that may stay in flight: the stores of iterations
-        // i-2 and i-1 and the DMA of group i+1
-        const int younger = ST * fin_prev2 + 5 * (i + 1 < nit) + ST * fin_prev1;
-        if constexpr (ABL & 16) t_a = rt_now();
-        if constexpr (ABL & 4) vm_wait(0); else vm_wait(younger);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // DMA of group i and the O writes of iteration i-1 visible
-        if constexpr (ABL & 16) {
-            const unsigned long long t = rt_now();
-            t_wait += t - t_a;
-            t_a = t;
-        }
-        const bool dma_on = !(ABL & 4) && i + 2 < nit;
-        if constexpr (ABL & 64) {  // tuning: the group's DMA right after the barrier instead of in gaps 1..5
-            if (dma_on) {
-#pragma unroll
-                for (int j = 0; j < ROW_INSTR; ++j) dma(i + 2, j);
-            }
-        }
-        const bool wprev = i >= 1 && i <= nit;  // O writes of T row 4(i-1)+w
-        float* wrow = T + ((GR * (i - 1) + wave - wky) & (NT - 1)) * (TW * TS) + 4 * hh * TS + wpos;
-        auto owrite = [&](int g) { wrow[((g & 3) + 8 * (g >> 2)) * TS] = accp[g]; };
-
-        // finish output row ys + r0 (O row r0 complete: T rows r0 .. r0+8 written by iteration i-1)
-        const bool fin = !(ABL & 2) && i >= 4;
-        const int r0 = GR * (i - 4) + wave;
-        f32x4 t4[5];  // lanes 0..31: O terms of channels 0 (t 0..8) and 1 (t 9..17); 32..63: channel 2 (t 0..8)
-        if (fin) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k)
-                t4[k] = lds_read16f4_async((const char*)(T + (r0 & (NT - 1)) * (TW * TS) + l31 * TS + 20 * hh + 4 * k));
-        }
-        const int yy = ys + r0, xx = x0 + l31;
-        const bool valid = yy < d.h && xx < d.w;
-        float sA = biasA, sB = biasB;
-        auto tv = [&](int n) { return t4[n >> 2][n & 3]; };
-        auto store = [&](float sv, int co, bool ok) {
-            const float t = tanhf(sv);
-            const int off = ok ? (int)((co * plane + (size_t)yy * d.w + xx) * esz) : 0x7ffffff0;
-            if (d.y_u8) {
-                const float q = rintf((t + 1.f) / 2.f * 255.f);
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)fminf(fmaxf(q, 0.f), 255.f), yrs, off, 0, 0);
-            } else {
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, t), yrs, off, 0, 0);
-            }
-        };
-
-        if (i < nit) {
-            // T row 4i + wave: the 1x9 row conv, k-steps in the per-tile kernels' order (chunk, kx, ks)
-            const char* row = smem + OFF_IN + ((i % NG) * GR + wave) * ROWB;
-            f32x16 acc;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-            bf16x8 fa[PD];
-            auto rd = [&](int st_, int slot) {
-                const int chunk = st_ / 18, kx = (st_ / 2) % 9, ks = st_ & 1;
-                fa[slot] = lds_read16_async(row + (chunk * 2 + ks) * (2 * HC) * 16 + halo_unit2(kx + l31, hh) * 16);
-            };
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s2 = 0; s2 < PD; ++s2) rd(s2, s2);
-#pragma unroll
-            for (int s2 = 0; s2 < 36; ++s2) {
-                // younger reads allowed in flight: those of steps s2+1 .. min(s2+PD-1, 35)
-                const int younger_rd = (35 - s2) < (PD - 1) ? (35 - s2) : (PD - 1);
-                if (s2 == 0) {
-                    lds_wait_t<PD - 1>(fa[0], t4);  // the older O-ring reads have landed as well
-                } else {
-                    switch (younger_rd) {
-                        case 11: lds_wait1<11>(fa[s2 % PD]); break;
-                        case 10: lds_wait1<10>(fa[s2 % PD]); break;
-                        case 9: lds_wait1<9>(fa[s2 % PD]); break;
-                        case 8: lds_wait1<8>(fa[s2 % PD]); break;
-                        case 7: lds_wait1<7>(fa[s2 % PD]); break;
-                        case 6: lds_wait1<6>(fa[s2 % PD]); break;
-                        case 5: lds_wait1<5>(fa[s2 % PD]); break;
-                        case 4: lds_wait1<4>(fa[s2 % PD]); break;
-                        case 3: lds_wait1<3>(fa[s2 % PD]); break;
-                        case 2: lds_wait1<2>(fa[s2 % PD]); break;
-                        case 1: lds_wait1<1>(fa[s2 % PD]); break;
-                        default: lds_wait1<0>(fa[s2 % PD]); break;
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ABL & 1) {
-                    asm volatile("" ::"v"(fa[s2 % PD]), "v"(wr[s2]));
-                } else {
-                    acc = mfma32(fa[s2 % PD], wr[s2], acc);
-                }
-                if (s2 + PD < 36) rd(s2 + PD, s2 % PD);
-                // side jobs in this gap (see the schedule above)
-                if (!(ABL & 64) && s2 >= 1 && s2 <= ROW_INSTR && dma_on) dma(i + 2, s2 - 1);
-                if (s2 >= 6 && s2 < 22 && wprev) owrite(s2 - 6);
-                if (fin) {
-                    if (s2 >= 1 && s2 <= 9) {  // same order as the per-tile kernels: bias, ky 0..8
-                        sA += tv(s2 - 1);
-                        sB += tv(9 + s2 - 1);
-                    }
-                    if (s2 == 12) store(sA, cA, valid);
-                    if (s2 == 24) store(sB, 1, valid && hh == 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            accp = acc;
-        } else {
-            if (wprev) {
-#pragma unroll
-                for (int g = 0; g < 16; ++g) owrite(g);
-            }
-            if (fin) {
-                lds_wait_t4<0>(t4);
-#pragma unroll
-                for (int ky = 0; ky < 9; ++ky) {
-                    sA += tv(ky);
-                    sB += tv(9 + ky);
-                }
-                store(sA, cA, valid);
-                store(sB, 1, valid && hh == 0);
-            }
-        }
-        if constexpr (ABL & 16) t_loop += rt_now() - t_a;
-    }
-#ifdef ISR_TUNING
-    if constexpr (ABL & 16) {
-        unsigned long long* p = g_tail_stamps;
-        if (p != nullptr && lane == 0) {
-            unsigned long long* q = p + ((size_t)blockIdx.x * WM + wave) * 4;
-            q[0] = t_entry;
-            q[1] = rt_now();
-            q[2] = t_wait;
-            q[3] = t_loop;
-        }
-    }
-#endif
-}
-
-// ---- row-streaming tail, 8 waves (variant 5): the variant-4 walk with two waves per SIMD.
-// One wave per SIMD left every non-MFMA cost of the wave (LDS-DMA issue, the finish's VALU,
-// LDS waits) on the MFMA chain's critical path; with a partner wave those stalls overlap the
-// partner's MFMAs.  Eight T rows per iteration (one per wave), input rows double-buffered
-// (group i+1's DMA issued in the gaps of iteration i), the O ring (keyed by output row, as in
-// variant 4) written at the end of the iteration; after barrier #2 the next iteration reads its
-// O terms into registers before its top barrier, so O row r0 lives two iterations: 16 rows.
-// Bit-identical to variants 1/3/4 (same MFMA order per T element, same ky-sum order).
+// ---- row-streaming tail, 8 waves (variant 5): no recomputed rows.  A block owns a 32-column
+// strip of one image over `sh` output rows and walks DOWN it: each wave turns one input row into
+// its T row (the 1x9 row conv, N = (ky, co)) with 36 MFMAs, every T row is computed once (the
+// per-tile kernel recomputes the 8 halo rows of every tile: 2x the MFMA work), and output row y is
+// finished once T rows y-4 .. y+4 exist.  The T terms go to a 16-row ring keyed by the output row
+// they feed (O[r0][px][pos(co, ky)] = T(r0+ky)[px][ky*3+co]).  The 36 weight fragments stay in
+// VGPRs (one LDS read per MFMA instead of two: with weights in LDS the waves' fragment reads
+// saturated the LDS port before the MFMAs did).  Two waves per SIMD: the non-MFMA costs of a wave
+// (LDS-DMA issue, the finish's VALU, LDS waits) overlap its partner's MFMAs.  Eight T rows per
+// iteration (one per wave), input rows double-buffered (group i+1's DMA issued in the gaps of
+// iteration i), the O ring written at the end of the iteration; after barrier #2 the next
+// iteration reads its O terms into registers before its top barrier, so O row r0 lives two
+// iterations: 16 rows.  The finish of an older output row (ky sums, tanh, 2 stores) is interleaved
+// into the MFMA sequence of the current T row.  Bit-identical to variant 3.
+// LDS reads of the loop are asm (lds_read16_async / lds_read16f4_async) with counted lgkmcnt
+// waits: hipcc's own waits here were lgkmcnt(0) every few MFMAs.  Counted vmcnt: per wave,
+// 5 LDS-DMA per row group and exactly 2 stores per finished row.
 namespace tail8w {
 constexpr int TW = 32, WM = 8, GR = 8;       // strip width, waves, rows per group (one per wave)
 constexpr int HC = TW + 8;
@@ -909,17 +341,17 @@ constexpr int ROWB = 4 * HC * 32;             // 5120
 constexpr int ROW_INSTR = ROWB / 1024;        // 5
 constexpr int NG = 2;
 constexpr int NT = 16;
-constexpr int TS = tails::TS;                 // O row as in variant 4: [px][co 0: 0..8, co 1: 9..17, co 2: 20..28]
+constexpr int TS = 36;                        // O row: [px][co 0: 0..8, co 1: 9..17, co 2: 20..28] + pad (conflict-free 16-B px reads)
 constexpr int TROW = TW * TS * 4;             // 4608
 constexpr int OFF_IN = 0;
 constexpr int OFF_T = OFF_IN + NG * GR * ROWB;      // 81920
 constexpr int LDS = OFF_T + NT * TROW + 64;        // 155712 (+64: lanes 32..63 of px 31 read 4 floats past a row)
-constexpr int PD = 4;
-constexpr int ST = 2;
+constexpr int PD = 4;                          // A-fragment prefetch distance (MFMA steps)
+constexpr int ST = 2;                          // stores per finished row per wave
 static_assert(LDS <= 163840, "LDS");
 }  // namespace tail8w
 
-template <int ABL, int PD = tail8w::PD, bool H = false>
+template <bool H = false>
 __global__ __launch_bounds__(512, 1) void tail9x9_stream8_kernel(isr_tail_desc d, int sh) {
     using namespace tail8w;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -980,7 +412,7 @@ __global__ __launch_bounds__(512, 1) void tail9x9_stream8_kernel(isr_tail_desc d
     auto tv = [&](int n) { return t4[n >> 2][n & 3]; };
 
     for (int i = 0; i <= nit; ++i) {
-        const bool fin = !(ABL & 2) && i >= 2;
+        const bool fin = i >= 2;
         // this iteration's O terms (output row ys + 8(i-2) + wave): the O ring is complete up to
         // it since barrier #2 of the previous iteration.  Issued here, at the top, so no asm
         // load is in flight across the loop's back-edge (the compiler may copy such registers)
@@ -991,13 +423,12 @@ __global__ __launch_bounds__(512, 1) void tail9x9_stream8_kernel(isr_tail_desc d
                 t4[k] = lds_read16f4_async((const char*)(T + (r0 & (NT - 1)) * (TW * TS) + l31 * TS + 20 * hh + 4 * k));
         }
         // own row of group i landed; younger VMEM: the stores of iteration i-1
-        const int younger = ST * (!(ABL & 2) && i - 1 >= 2);
-        if (ABL & 4) vm_wait(0); else vm_wait(younger);
+        vm_wait(ST * (i - 1 >= 2));
         lds_wait_t4<0>(t4);
         // top barrier: LDS-DMA data (vmcnt, then a barrier, then ds_read), and every wave holds
         // its O terms, so their ring slots may be rewritten by this iteration's T writes
         __builtin_amdgcn_s_barrier();
-        const bool dma_on = !(ABL & 4) && i + 1 < nit;
+        const bool dma_on = i + 1 < nit;
         const int yy = ys + r0, xx = x0 + l31;
         const bool valid = yy < d.h && xx < d.w;
         float sA = biasA, sB = biasB;
@@ -1029,19 +460,13 @@ __global__ __launch_bounds__(512, 1) void tail9x9_stream8_kernel(isr_tail_desc d
             for (int s2 = 0; s2 < 36; ++s2) {
                 const int younger_rd = (35 - s2) < (PD - 1) ? (35 - s2) : (PD - 1);
                 switch (younger_rd) {
-                    case 5: lds_wait1<5>(fa[s2 % PD]); break;
-                    case 4: lds_wait1<4>(fa[s2 % PD]); break;
                     case 3: lds_wait1<3>(fa[s2 % PD]); break;
                     case 2: lds_wait1<2>(fa[s2 % PD]); break;
                     case 1: lds_wait1<1>(fa[s2 % PD]); break;
                     default: lds_wait1<0>(fa[s2 % PD]); break;
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ABL & 1) {
-                    asm volatile("" ::"v"(fa[s2 % PD]), "v"(wr[s2]));
-                } else {
-                    acc = mfma32t<H>(fa[s2 % PD], wr[s2], acc);
-                }
+                acc = mfma32t<H>(fa[s2 % PD], wr[s2], acc);
                 if (s2 + PD < 36) rd(s2 + PD, s2 % PD);
                 if (s2 >= 1 && s2 <= ROW_INSTR && dma_on) dma(i + 1, s2 - 1);
                 if (fin) {
@@ -1069,186 +494,6 @@ __global__ __launch_bounds__(512, 1) void tail9x9_stream8_kernel(isr_tail_desc d
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // barrier #2: every T row of iteration i is in the O ring
-    }
-}
-
-// ---- lane-streaming tail (variant 6): one WAVE walks one 32-column strip down `sh` output rows,
-// with no barriers and no cross-wave state.  Per input row: the 36-MFMA chain gives T[px][n'] with
-// the weight columns permuted to n' = co*9 + ky + 1, so the nine ky terms of one channel sit in
-// nine adjacent lanes; a running partial sum P (16 px per lane) then advances ONE lane per row:
-// P[n'] <- P[n'-1] (v_add_f32 with DPP wave_shr:1) + T[n'].  Output row y's channel-co sum is
-// bias (injected at lane 9co) + T(y-4)[ky 0] + ... + T(y+4)[ky 8], added in exactly that order —
-// the per-tile kernels' order — and complete in lane 9co+9 one row after its last term: written
-// to a small per-wave LDS buffer, then tanh'ed and stored two output rows at a time with all 64
-// lanes busy.  Input rows stream through a per-wave 3-row LDS ring (LDS-DMA two rows ahead,
-// waited by counted vmcnt: same wave, no barrier).  Bit-identical to variants 1/3/4/5.
-namespace tailw {
-constexpr int TW = 32, WPB = 4;               // strip width, waves per block (independent)
-constexpr int HC = TW + 8;
-constexpr int ROWB = 4 * HC * 32;             // 5120: one input row image
-constexpr int ROW_INSTR = ROWB / 1024;        // 5
-constexpr int NR = 3;                         // rows in a wave's ring
-constexpr int FB = 2 * 2 * 3 * TW * 4;        // finished-sum buffer: [slot 2][row 2][co 3][px 32] fp32 = 1536
-constexpr int WAVE_LDS = NR * ROWB + FB;      // 16896
-constexpr int LDS = WPB * WAVE_LDS;           // 67584: two blocks per CU
-constexpr int PD = 2;
-constexpr int FLUSH_ST = 3;                   // stores per flush (2 rows x 3 co x 32 px over 64 lanes)
-static_assert(2 * LDS <= 163840, "two blocks per CU");
-}  // namespace tailw
-
-__device__ __forceinline__ float dpp_shr1(float v) {  // lane i <- lane i-1 (lane 0 <- 0)
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
-
-template <int ABL, int MINB = 2>
-__global__ __launch_bounds__(256, MINB) void tail9x9_lane_kernel(isr_tail_desc d, int sh, int nwaves) {
-    using namespace tailw;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int wave = wave_id();
-    const int lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
-    const int nstrip = d.wa / TW, nseg = d.ha / sh;
-    int gw = xcd_remap(blockIdx.x, gridDim.x) * WPB + wave;  // neighbouring strips in one block / XCD
-    if (gw >= nwaves) return;  // whole wave (no barriers in this kernel)
-    const int strip = gw % nstrip;
-    gw /= nstrip;
-    const int seg = gw % nseg;
-    const int img = gw / nseg;
-    const int x0 = strip * TW, ys = seg * sh;
-    const int nt = sh + 8;  // T rows ys-4 .. ys+sh+3
-    char* ring = smem + wave * WAVE_LDS;
-    float* fbuf = reinterpret_cast<float*>(ring + NR * ROWB);
-    const size_t pstride = plane_bytes(d.x);
-    const char* xcol = view_at(d.x, img, 0, x0 - 4, 0);
-    const int xrow = d.x.wp * 32;
-
-    auto dma = [&](int t, int j) {  // input row of T row t (= image row ys-4+t) into ring slot t % NR
-        const int u = j * 64 + lane;  // 16-byte unit of the row image
-        const int p = u / (2 * HC), r = u - p * 2 * HC;
-        const int q = r >> 1, c = (r & 1) ^ ((q >> 3) & 1);
-        glds16(xcol + (ptrdiff_t)(ys - 4 + t) * xrow + (size_t)p * pstride + q * 32 + c * 16,
-               ring + (t % NR) * ROWB + j * 1024);
-    };
-    // B fragments with the permuted columns: lane column n' = co*9 + ky + 1 takes packed n = ky*3 + co
-    const int np = l31 - 1;
-    const bool wcol = np >= 0 && np < 27;
-    const int wco = wcol ? np / 9 : 0, wky = wcol ? np - 9 * (np / 9) : 0;
-    const int pn = wky * 3 + wco;
-    bf16x8 wr[36];
-#pragma unroll
-    for (int st = 0; st < 36; ++st) {
-        const int chunk = st / 18, kx = (st / 2) % 9, ks = st & 1;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(
-            (const char*)d.wpack + ((((kx * 2 + chunk) * 2 + ks) * 32 + pn) * 2 + (hh ^ ((pn >> 3) & 1))) * 16);
-        wr[st] = wcol ? v : bf16x8{};
-    }
-#pragma unroll
-    for (int j = 0; j < ROW_INSTR; ++j) dma(0, j);
-#pragma unroll
-    for (int j = 0; j < ROW_INSTR; ++j) dma(1, j);
-
-    // bias injection: lane 9co (co = 0, 1, 2) holds bias[co] before the shift, which lane 9co+1 reads
-    const bool inj = l31 == 0 || l31 == 9 || l31 == 18;
-    const float binj = d.bias ? d.bias[l31 == 0 ? 0 : l31 == 9 ? 1 : 2] : 0.f;
-    const bool done_lane = l31 == 9 || l31 == 18 || l31 == 27;  // ky = 8 of channel (l31 - 9) / 9
-    const int dco = l31 / 9 - 1;
-
-    const size_t plane = (size_t)d.h * d.w;
-    const int esz = d.y_u8 ? 1 : 4;
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)d.y + (size_t)img * 3 * plane * esz, (short)0, (int)(3 * plane * esz), 0x00020000);
-
-    f32x16 P;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) P[g] = 0.f;
-    // flush of the finished pair in slot fs (output rows ys + 2*pr, +1): 3 values per lane
-    float fv[3];
-    int fpr = 0;
-    auto flush_read = [&](int fs) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) fv[j] = fbuf[fs * 192 + j * 64 + lane];
-    };
-    auto flush_store = [&](int j) {  // element k = j*64 + lane of [row 2][co 3][px 32]
-        const int k = j * 64 + lane;
-        const int rr = k / 96, co = (k / 32) % 3, px = k & 31;
-        const int yy = ys + 2 * fpr + rr, xx = x0 + px;
-        const float t = tanhf(fv[j]);
-        const int off = (yy < d.h && xx < d.w) ? (int)((co * plane + (size_t)yy * d.w + xx) * esz) : 0x7ffffff0;
-        if (d.y_u8) {
-            const float q = rintf((t + 1.f) / 2.f * 255.f);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)fminf(fmaxf(q, 0.f), 255.f), yrs, off, 0, 0);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, t), yrs, off, 0, 0);
-        }
-    };
-
-    for (int t = 0; t < nt; ++t) {
-        // row t landed.  Younger VMEM ops possibly in flight: the flush stores of rows t-2 and
-        // t-1 (a flush runs in even rows >= 10) and the DMA of row t+1
-        auto flushes = [&](int u) { return u >= 10 && (u & 1) == 0 && !(ABL & 2); };
-        const int younger = FLUSH_ST * flushes(t - 2) + ROW_INSTR * (t + 1 < nt) + FLUSH_ST * flushes(t - 1);
-        if (ABL & 4) vm_wait(0); else vm_wait(younger);
-        const bool dma_on = !(ABL & 4) && t + 2 < nt;
-        const bool fl = flushes(t);
-        if (fl) fpr = (t - 10) / 2;  // output pair (rows ys + 2*fpr, +1) finished in rows t-2, t-1
-
-        const char* row = ring + (t % NR) * ROWB;
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-        bf16x8 fa[PD];
-        auto rd = [&](int st_, int slot) {
-            const int chunk = st_ / 18, kx = (st_ / 2) % 9, ks = st_ & 1;
-            fa[slot] = lds_read16_async(row + (chunk * 2 + ks) * (2 * HC) * 16 + halo_unit2(kx + l31, hh) * 16);
-        };
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s2 = 0; s2 < PD; ++s2) rd(s2, s2);
-#pragma unroll
-        for (int s2 = 0; s2 < 36; ++s2) {
-            const int younger_rd = (35 - s2) < (PD - 1) ? (35 - s2) : (PD - 1);
-            switch (younger_rd) {
-                case 3: lds_wait1<3>(fa[s2 % PD]); break;
-                case 2: lds_wait1<2>(fa[s2 % PD]); break;
-                case 1: lds_wait1<1>(fa[s2 % PD]); break;
-                default: lds_wait1<0>(fa[s2 % PD]); break;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (ABL & 1) {
-                asm volatile("" ::"v"(fa[s2 % PD]), "v"(wr[s2]));
-            } else {
-                acc = mfma32(fa[s2 % PD], wr[s2], acc);
-            }
-            if (s2 + PD < 36) rd(s2 + PD, s2 % PD);
-            if (s2 >= 1 && s2 <= ROW_INSTR && dma_on) dma(t + 2, s2 - 1);
-            if (fl) {
-                if (s2 == 6) flush_read(((t - 10) / 2) & 1);
-                if (s2 == 12) flush_store(0);
-                if (s2 == 20) flush_store(1);
-                if (s2 == 28) flush_store(2);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // running sums: inject the biases, shift one lane, add this row's terms
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const float pin = inj ? binj : P[g];
-            P[g] = dpp_shr1(pin) + acc[g];
-        }
-        // lanes 9/18/27 now hold output row ys + t - 8 of channel dco: to the flush buffer
-        if (t >= 8 && done_lane) {
-            const int u = t - 8;  // output row index in the segment
-            float* fr = fbuf + ((u >> 1) & 1) * 192 + (u & 1) * 96 + dco * 32 + 4 * hh;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) fr[(g & 3) + 8 * (g >> 2)] = P[g];
-        }
-    }
-    // the last pair (rows sh-2, sh-1), finished in rows nt-2, nt-1
-    if (!(ABL & 2)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        fpr = (sh - 2) / 2;
-        flush_read(fpr & 1);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) flush_store(j);
     }
 }
 
@@ -1283,186 +528,39 @@ int head9x9_fwd_dispatch(const isr_head_desc* d, hipStream_t s) {
     return d->f16 ? go(head9x9_kernel<true>) : go(head9x9_kernel<false>);
 }
 
+// variant 0 = production = 5, the 8-wave row-streaming walk (170-177 us at 16 x 512^2, fp32 out,
+// against 354-375 us for the 8-row per-tile kernel, variant 3); 3 is also the fallback of images
+// whose output passes 2 GiB (the walk stores through 32-bit offsets).  -2: any other id.
 int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s) {
-    // production = variant 5, the 8-wave row-streaming walk: 170-177 us at 16 x 512² (fp32
-    // out) vs 354-375 us for the 8-row per-tile kernel (variant 3), 259-280 us for the 4-wave
-    // walk (4) and 236-280 us for the lane-streaming walk (6), all bit-identical
-    // (tools/tune_tail.py, tests/test_gpu_kernels.py); the persistent variant 2 measures 515 us
     if (variant == 0) variant = 5;
-    if (d->f16) {  // fp16 activations (the inference path): the production walk and its fallback only
-        if (variant != 5 && variant != 3) return -2;
-        if (variant == 5 && (size_t)3 * d->h * d->w * (d->y_u8 ? 1 : 4) >= ((size_t)1 << 31)) variant = 3;
-        if (variant == 3) {
-            lds_limit((const void*)tail9x9_k8_kernel<true>, tail8::LDS);
-            dim3 grid8(d->wa / tail8::TW, d->ha / tail8::TH, d->n);
-            hipLaunchKernelGGL(tail9x9_k8_kernel<true>, grid8, dim3(256), tail8::LDS, s, *d);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        }
-    }
-#ifndef ISR_TUNING
-    // production: the row-streaming walk (5) and the 8-row per-tile kernel (3, the fallback of
-    // images whose fp32 output passes 2 GiB); the other forms are in the tuning library only
     if (variant != 3 && variant != 5) return -2;
-#endif
-#ifdef ISR_TUNING
-    if (variant == 2 || (variant >= 10 && variant <= 17)) {  // persistent
-        const int cus = cu_count();
-        const int ntiles = d->n * (d->ha / tail::TH) * (d->wa / tail::TW);
-        const int grid = ntiles < cus ? ntiles : cus;
-        auto go = [&](auto kern) {
-            lds_limit((const void*)kern, tailp::LDS);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), tailp::LDS, s, *d, ntiles);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        };
-        switch (variant) {
-#ifdef ISR_TUNING
-            case 12: return go(tail9x9_pkernel<2>);  // timing probes, outputs wrong: tuning builds only
-            case 13: return go(tail9x9_pkernel<8>);
-#endif
-            default: return go(tail9x9_pkernel<0>);
-        }
-    }
-#endif
-    [[maybe_unused]] int abl = 0, lane_sh = 0;
-#ifdef ISR_TUNING
-    if (variant >= 20 && variant < 70) {  // 20 + ABL: stream-tail ablations
-        abl = variant - 20;
-        variant = 4;
-    } else if (variant >= 70 && variant < 78) {  // 70 + ABL: 8-wave stream-tail ablations
-        abl = variant - 70;
-        variant = 5;
-    } else if (variant >= 80 && variant < 88) {  // 80 + ABL: lane-streaming ablations
-        abl = variant - 80;
-        variant = 6;
-    } else if (variant >= 90 && variant < 98) {  // 90 + log2(sh): lane-streaming segment height
-        lane_sh = 1 << (variant - 90);
-        variant = 6;
-    } else if (variant >= 100 && variant < 108) {  // 100 + log2(sh): one wave per SIMD
-        lane_sh = 1 << (variant - 100);
-        abl = 8;
-        variant = 6;
-    } else if (variant >= 110 && variant < 118) {  // the same without row DMA
-        lane_sh = 1 << (variant - 110);
-        abl = 9;
-        variant = 6;
-    }
-#endif
-    if ((variant == 4 || variant == 5 || variant == 6) && (size_t)3 * d->h * d->w * (d->y_u8 ? 1 : 4) >= ((size_t)1 << 31)) variant = 3;  // 32-bit store offsets
-#ifdef ISR_TUNING
-    if (variant == 6) {
-        int sh = lane_sh;
-        if (sh == 0) {
-            sh = 64;
-            while (d->ha % sh) sh >>= 1;
-        }
-        if (sh < 8 || d->ha % sh) return -2;
-        const int nwaves = d->n * (d->wa / tailw::TW) * (d->ha / sh);
-        const int blocks = (nwaves + tailw::WPB - 1) / tailw::WPB;
-        auto go = [&](auto kern) {
-            lds_limit((const void*)kern, tailw::LDS);
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), tailw::LDS, s, *d, sh, nwaves);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        };
-        switch (abl) {
-#ifdef ISR_TUNING
-            case 1: return go(tail9x9_lane_kernel<1>);
-            case 2: return go(tail9x9_lane_kernel<2>);
-            case 4: return go(tail9x9_lane_kernel<4>);
-            case 7: return go(tail9x9_lane_kernel<7>);
-            case 8: return go(tail9x9_lane_kernel<0, 1>);  // one wave per SIMD (no register cap)
-            case 9: return go(tail9x9_lane_kernel<4, 1>);
-#endif
-            default: return go(tail9x9_lane_kernel<0>);
-        }
-    }
-#endif
-    if (variant == 5) {
-        // segment height: the longest walk (<= 512 rows) that still gives every CU a strip —
-        // fewer, longer walks recompute fewer halo T rows and leave no partial last wave of
-        // blocks: 16x512^2 fp32 179 us at 128 rows, 164 at 256, 157 at 512 (tools/tune_tail.py
-        // with ISR_TAIL_SH, profiles/r02_tail_sh.jsonl)
-        int sh = 512;
-        while (sh > 8 && (d->ha % sh || (long)d->n * (d->wa / tail8w::TW) * (d->ha / sh) < cu_count())) sh >>= 1;
-#ifdef ISR_TUNING
-        if (const char* e = getenv("ISR_TAIL_SH")) sh = atoi(e);  // segment-height probe (tuning builds)
-#endif
-        while (d->ha % sh) sh >>= 1;
-        if (sh < 8) return -2;
-        const int blocks = d->n * (d->wa / tail8w::TW) * (d->ha / sh);
-        auto go = [&](auto kern) {
-            lds_limit((const void*)kern, tail8w::LDS);
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), tail8w::LDS, s, *d, sh);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        };
-        switch (abl) {
-#ifdef ISR_TUNING
-            case 1: return go(tail9x9_stream8_kernel<1>);
-            case 2: return go(tail9x9_stream8_kernel<2>);
-            case 4: return go(tail9x9_stream8_kernel<4>);
-            case 7: return go(tail9x9_stream8_kernel<7>);
-            case 3: return go(tail9x9_stream8_kernel<0, 3>);
-            case 5: return go(tail9x9_stream8_kernel<0, 5>);
-            case 6: return go(tail9x9_stream8_kernel<0, 6>);
-#endif
-            default: return d->f16 ? go(tail9x9_stream8_kernel<0, tail8w::PD, true>) : go(tail9x9_stream8_kernel<0>);
-        }
-    }
-#ifdef ISR_TUNING
-    if (variant == 4) {
-        // segment height: 8 T rows per segment are recomputed by the neighbour (6 % at 128)
-        int sh = 128;
-        while (d->ha % sh) sh >>= 1;
-        if (sh < 8) return -2;
-        const int blocks = d->n * (d->wa / tails::TW) * (d->ha / sh);
-        auto go = [&](auto kern) {
-            lds_limit((const void*)kern, tails::LDS);
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), tails::LDS, s, *d, sh);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        };
-        switch (abl) {
-#ifdef ISR_TUNING
-            case 1: return go(tail9x9_stream_kernel<1>);
-            case 2: return go(tail9x9_stream_kernel<2>);
-            case 3: return go(tail9x9_stream_kernel<3>);
-            case 4: return go(tail9x9_stream_kernel<4>);
-            case 5: return go(tail9x9_stream_kernel<5>);
-            case 6: return go(tail9x9_stream_kernel<6>);
-            case 7: return go(tail9x9_stream_kernel<7>);
-            case 16: return go(tail9x9_stream_kernel<16>);
-            case 49: return go(tail9x9_stream_kernel<64>);  // variant 69: DMA right after the barrier
-            case 32 + 4: return go(tail9x9_stream_kernel<0, 4>);  // 20 + 32 + PD: prefetch distance
-            case 32 + 8: return go(tail9x9_stream_kernel<0, 8>);
-            case 32 + 10: return go(tail9x9_stream_kernel<0, 10>);
-            case 32 + 12: return go(tail9x9_stream_kernel<0, 12>);
-#endif
-            default: return go(tail9x9_stream_kernel<0>);
-        }
-    }
-#endif
+    if (variant == 5 && (size_t)3 * d->h * d->w * (d->y_u8 ? 1 : 4) >= ((size_t)1 << 31)) variant = 3;
     if (variant == 3) {
-        lds_limit((const void*)tail9x9_k8_kernel<false>, tail8::LDS);
-        dim3 grid8(d->wa / tail8::TW, d->ha / tail8::TH, d->n);
-        hipLaunchKernelGGL(tail9x9_k8_kernel<false>, grid8, dim3(256), tail8::LDS, s, *d);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+        auto go = [&](auto kern) {
+            lds_limit((const void*)kern, tail8::LDS);
+            hipLaunchKernelGGL(kern, dim3(d->wa / tail8::TW, d->ha / tail8::TH, d->n), dim3(256), tail8::LDS, s, *d);
+            return hipGetLastError() == hipSuccess ? 0 : -1;
+        };
+        return d->f16 ? go(tail9x9_k8_kernel<true>) : go(tail9x9_k8_kernel<false>);
     }
-#ifdef ISR_TUNING
-    if (variant != 1) return -2;
-    lds_limit((const void*)tail9x9_kernel, tail::LDS);
-    dim3 grid(d->wa / tail::TW, d->ha / tail::TH, d->n);
-    hipLaunchKernelGGL(tail9x9_kernel, grid, dim3(256), tail::LDS, s, *d);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-#else
-    return -2;
-#endif
+    // segment height: the longest walk (<= 512 rows) that still gives every CU a strip — fewer,
+    // longer walks recompute fewer halo T rows and leave no partial last wave of blocks:
+    // 16x512^2 fp32 179 us at 128 rows, 164 at 256, 157 at 512 (profiles/r02_tail_sh.jsonl)
+    int sh = 512;
+    while (sh > 8 && (d->ha % sh || (long)d->n * (d->wa / tail8w::TW) * (d->ha / sh) < cu_count())) sh >>= 1;
+    while (d->ha % sh) sh >>= 1;
+    if (sh < 8) return -2;
+    const int blocks = d->n * (d->wa / tail8w::TW) * (d->ha / sh);
+    auto go = [&](auto kern) {
+        lds_limit((const void*)kern, tail8w::LDS);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), tail8w::LDS, s, *d, sh);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    };
+    return d->f16 ? go(tail9x9_stream8_kernel<true>) : go(tail9x9_stream8_kernel<false>);
 }
 
-#ifdef ISR_TUNING
-int tail_stamps_set(void* buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_tail_stamps), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-#else
+// no shipping tail kernel writes stamps (only the removed 4-wave walk did)
 int tail_stamps_set(void*) { return -2; }
-#endif
 
 int tail9x9_fwd_dispatch(const isr_tail_desc* d, hipStream_t s) { return tail9x9_fwd_variant(d, 0, s); }
 

@@ -3,9 +3,9 @@
 // conv (4 growth convs 64+32k -> 32 + LeakyReLU; the final 192 -> 64 conv with the RDB and
 // RRDB residuals) of every block, with tile-level dependencies instead of kernel boundaries.
 //
-// Round-3 design.  The round-2 chain (conv3x3.hip conv_chain_kernel) ran every (layer, tile)
-// as an independent conv tile: descriptor round trips, a pipeline fill, the dependency wait,
-// the pipeline drain, the store drain — per tile and per layer, ~45 % of every RDB.  Here a
+// Running every (layer, tile) as an independent conv tile (the first persistent chain, removed:
+// DESIGN.md section 5) paid descriptor round trips, a pipeline fill, the dependency wait, the
+// pipeline drain and the store drain per tile and per layer, ~45 % of every RDB.  Here a
 // workgroup runs ONE continuous stream of K-chunks over its (layer, tile) items:
 //  * the 2-slot LDS ring never drains at a tile or layer boundary: the first chunk of the next
 //    (layer, tile) is staged by LDS-DMA while the current tile's last chunk computes;
@@ -19,8 +19,8 @@
 //  * the RDB residual r1 = x[0:64] (the conv's own input) is added by four extra MFMAs per chunk
 //    on the already-staged centre pixels (A = (1/s1) I, exact in bf16 for add_rate 0.2) instead
 //    of re-reading 64 KB per tile in the epilogue: out = (acc + x/s1) * s1.  conv3x3.hip applies
-//    the same fold at the same point of the same MFMA order, so the per-conv launches and the
-//    round-2 chain stay bit-identical to this kernel.
+//    the same fold at the same point of the same MFMA order, so the per-conv launches stay
+//    bit-identical to this kernel.
 // Hand-off (cdna_hip_programming.md Guideline 16, R1): write-through (sc1) output stores,
 // drained by every wave before a workgroup barrier and a relaxed agent-scope progress store;
 // consumers poll the 9 neighbour words (sc1 loads, per wave) and read activations with sc1
@@ -168,17 +168,6 @@ __device__ __forceinline__ void trunk_stamp(int L, int t, int ntiles, int slot) 
 #endif
 }
 
-#if ISR_TRUNK_MFMA16_PROBE
-__device__ __forceinline__ f32x16 mfma32_probe16(bf16x8 a, bf16x8 b, f32x16 acc) {
-    f32x4 c0 = __builtin_shufflevector(acc, acc, 0, 1, 2, 3), c1 = __builtin_shufflevector(acc, acc, 4, 5, 6, 7);
-    c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c1, 0, 0, 0);
-    f32x4 c2 = __builtin_shufflevector(acc, acc, 8, 9, 10, 11), c3 = __builtin_shufflevector(acc, acc, 12, 13, 14, 15);
-    f32x8 lo = __builtin_shufflevector(c0, c1, 0, 1, 2, 3, 4, 5, 6, 7), hi = __builtin_shufflevector(c2, c3, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-}
-#endif
-
 // Tuning builds: ablation knobs (timing only, outputs wrong): bit 1 = no halo LDS-DMA after the
 // first item, 4 = no epilogue stores, 8 = no weight LDS-DMA, 16 = no dependency waits;
 // [1] = workgroups per CU (host side, 0 = occupancy).  (An MFMA ablation branch inside the step
@@ -223,36 +212,27 @@ __device__ __forceinline__ void glds4(const void* gsrc, void* lds) {
     __builtin_amdgcn_global_load_lds(gsrc, ISR_LDS_PTR(lds), 4, 0, 0);
 }
 
-// One kernel build: WM waves of R output rows each (the 16-row tile), an NST-slot LDS ring (NST-1
-// K-chunks in flight).  <4, 4, 2>: two 4-wave workgroups per CU, one chunk in flight (the
-// round-3 first form); <8, 2, 4>: one 8-wave workgroup per CU, three chunks in flight, two tiles
-// of independent images interleaved per layer.
-template <int WM_, int R_, int NST_, int TH_ = 16, int XM_ = 0, int NTP_ = 0>
+// The kernel's build: two 4-wave workgroups per CU (4 output rows per wave: the 16-row tile), a
+// 2-slot LDS ring (one K-chunk in flight), two fragment sets (the next dx step's fragments are read
+// during this step's MFMAs).  The forms that lost their A/B against it (deeper rings, 8-wave
+// workgroups, 32-row tiles, one fragment set, the XCD-aware tile deal, non-temporal cache policies)
+// were removed: DESIGN.md section 5.
 struct TK {
-    static constexpr int WM = WM_, R = R_, NST = NST_;
-    // NTP (A/B): non-temporal cache policy on the halo LDS-DMA (bit 0) / the output stores (bit 1)
-    static constexpr int HALO_AUX = 16 | ((NTP_ & 1) ? 2 : 0), STORE_AUX = 16 | ((NTP_ & 2) ? 2 : 0);
-    // XM = 1: XCD-aware tile deal — workgroup b (dispatched round-robin to XCD b % 8) works as
-    // virtual workgroup xcd_remap(b), so each XCD streams a contiguous range of tiles and a tile's
-    // halo neighbours were written through the same XCD's L2
-    static constexpr int XM = XM_;
+    static constexpr int WM = 4, R = 4, NST = 2;
+    static constexpr int HALO_AUX = 16, STORE_AUX = 16;  // sc1 on the halo LDS-DMA and the output stores
     static constexpr int NT = 64 * WM;
-    static constexpr int TH = TH_;                        // tile rows (x 32 columns)
+    static constexpr int TH = tk::TH;                     // tile rows (x 32 columns)
     static constexpr int HQ = (TH + 2) * tk::HC;          // halo pixels of a chunk
     static constexpr int HP = (HQ + 31) / 32;             // halo pieces (1 KB) per chunk
     static_assert(R * WM == TH, "the waves cover the tile rows");
-    static_assert(NST >= 2 && NST <= 4, "ring depth");
     static constexpr int HPW = (HP + WM - 1) / WM;        // halo pieces per wave (at most)
     static constexpr int WPW = (tk::WPF + WM - 1) / WM;  // weight pieces per wave (at most)
     static constexpr int SLOT = (HP + tk::WPF) * 1024;
     static constexpr int BIAS_OFF = NST * SLOT;          // 4 bias slots of 256 B
     static constexpr int LDS = BIAS_OFF + 4 * 256;
-    static_assert(LDS <= 163840, "LDS budget");
-    static constexpr int BPC = 163840 / LDS < 2 ? 163840 / LDS : 2;  // workgroups per CU
-    static constexpr int WPS = BPC * WM / 4;                          // waves per SIMD
-    // fragment sets: 2 (the next dx step's fragments read during this step's MFMAs) or, at 4 waves
-    // per SIMD (128 VGPRs), 1 — each step reads its own, the SIMD's other waves cover the latency
-    static constexpr int NSET = WPS >= 4 ? 1 : 2;
+    static constexpr int BPC = 2;                         // workgroups per CU
+    static_assert(BPC * LDS <= 163840, "LDS budget");
+    static constexpr int WPS = BPC * WM / 4;              // waves per SIMD
 };
 
 // Where the chunks of one (layer, tile) item come from (LDS-DMA through buffer resources:
@@ -266,9 +246,7 @@ struct Src {
     uint32_t xbytes, wbytes;  // extents of one activation plane and of the packed weights
 };
 
-template <class K>
 struct TrunkCtx {
-    static constexpr int TH = K::TH;
     unsigned* state;
     unsigned gen;
     int acquire;
@@ -276,16 +254,15 @@ struct TrunkCtx {
     uint32_t pstride;            // bytes per 16-channel plane (< 2 GiB: prep err bit 64); every buffer
                                  // resource spans ONE plane (a per-(image, plane) base), so the
                                  // buffers themselves may be any size (the 4K still, video batches)
-    uint32_t hoff[K::HPW];       // per-lane halo piece offsets (chunk-invariant)
+    uint32_t hoff[TK::HPW];       // per-lane halo piece offsets (chunk-invariant)
     int abl;                     // tuning ablation bits (0 in production builds)
 };
 
-template <class C>
-__device__ __forceinline__ Src src_of(const C& c, const_rec& rec, int t) {
+__device__ __forceinline__ Src src_of(const TrunkCtx& c, const_rec& rec, int t) {
     const int bx = t % c.nbx, tmp = t / c.nbx, by = tmp % c.nby, img = tmp / c.nby;
     Src s;
     s.x = (const char*)(uintptr_t)rec.x + (size_t)((uint32_t)img * c.cs16 + rec_xp(rec)) * c.pstride;
-    s.h0 = (uint32_t)(((by * C::TH - 1 + c.pad) * c.wp + (bx * tk::TW - 1 + c.pad)) * 32);
+    s.h0 = (uint32_t)(((by * TK::TH - 1 + c.pad) * c.wp + (bx * tk::TW - 1 + c.pad)) * 32);
     s.w = (const char*)(uintptr_t)rec.w;
     s.b = (const float*)(uintptr_t)rec.b;
     s.wpc = rec_kind(rec) == 1 ? tk::WPF : tk::WPG;  // 64 / 32 couts (kinds 0 and 2: 32)
@@ -298,31 +275,30 @@ __device__ __forceinline__ Src src_of(const C& c, const_rec& rec, int t) {
 // weight pieces; wave 0 also the bias (first chunk of a tile).  Halo pieces are sc1 (L1
 // bypass: other workgroups of this launch wrote them).  Returns the vector-memory instructions
 // this wave issued (wave-uniform), for the counted waits.
-template <int WM, int HPW, int WPW, int SLOTB, int BIASB, int HP, int HAUX = 16>
-__device__ __forceinline__ uint32_t stage_chunk_k(const uint32_t* hoff, uint32_t pstride, int abl, const Src& s,
-                                                  int chunk, int slot, bool with_bias, int bslot) {
+__device__ __forceinline__ uint32_t stage_pieces(const uint32_t* hoff, uint32_t pstride, int abl, const Src& s,
+                                                 int chunk, int slot, bool with_bias, int bslot) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = wave_id(), lane = threadIdx.x & 63;
-    char* dst = smem + slot * SLOTB;
+    char* dst = smem + slot * TK::SLOT;
     uint32_t n = 0;
     const auto rx = rsrc_n(s.x + (size_t)chunk * pstride, s.xbytes);  // chunk c = plane xp + c
     const uint32_t so = s.h0;
     if (!(abl & 1)) {
 #pragma unroll
-        for (int k = 0; k < HPW; ++k) {
-            const int j = wave + WM * k;
-            if (j < HP) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ISR_LDS_PTR(dst + j * 1024), 16, hoff[k], so, 0, HAUX);
+        for (int k = 0; k < TK::HPW; ++k) {
+            const int j = wave + TK::WM * k;
+            if (j < TK::HP) {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ISR_LDS_PTR(dst + j * 1024), 16, hoff[k], so, 0, TK::HALO_AUX);
                 ++n;
             }
         }
     }
     const auto rw = rsrc_n(s.w, s.wbytes);
     const uint32_t wo = (uint32_t)(chunk * s.wpc * 1024);
-    char* wd = dst + HP * 1024;
+    char* wd = dst + TK::HP * 1024;
 #pragma unroll
-    for (int k = 0; k < WPW; ++k) {
-        const int j = wave + WM * k;
+    for (int k = 0; k < TK::WPW; ++k) {
+        const int j = wave + TK::WM * k;
         if (j < s.wpc && !(abl & 8)) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(wd + j * 1024), 16, lane * 16, wo + j * 1024, 0, 0);
             ++n;
@@ -330,21 +306,20 @@ __device__ __forceinline__ uint32_t stage_chunk_k(const uint32_t* hoff, uint32_t
     }
     if (with_bias && wave == 0) {
         if (lane < (s.wpc == tk::WPG ? 32 : 64))  // cout floats only
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(s.b, s.wpc == tk::WPG ? 128u : 256u), ISR_LDS_PTR(smem + BIASB + bslot * 256), 4,
-                                                     lane * 4, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(s.b, s.wpc == tk::WPG ? 128u : 256u),
+                                                     ISR_LDS_PTR(smem + TK::BIAS_OFF + bslot * 256), 4, lane * 4, 0, 0, 0);
         ++n;
     }
     return n;
 }
 
-template <class K>
-__device__ __forceinline__ uint32_t stage_chunk(const TrunkCtx<K>& c, const Src& s, int chunk, int slot, bool with_bias,
+__device__ __forceinline__ uint32_t stage_chunk(const TrunkCtx& c, const Src& s, int chunk, int slot, bool with_bias,
                                                 int bslot) {
 #ifdef ISR_TUNING
     // tuning-build check of the ring protocol: the chunk lies inside the layer (chunk < nch: its
     // weights inside the packed table) and the slot inside the ring.  A violation gives the launch
     // up (the host raises) and issues nothing, instead of a DMA to a wrong place.
-    if (chunk < 0 || (uint32_t)(chunk * s.wpc * 1024) >= s.wbytes || slot < 0 || slot >= K::NST ||
+    if (chunk < 0 || (uint32_t)(chunk * s.wpc * 1024) >= s.wbytes || slot < 0 || slot >= TK::NST ||
         bslot < 0 || bslot > 3) {
         if (threadIdx.x == 0) {
             __hip_atomic_store(c.state + 1, c.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -353,133 +328,7 @@ __device__ __forceinline__ uint32_t stage_chunk(const TrunkCtx<K>& c, const Src&
         return 0;
     }
 #endif
-    if constexpr (K::NSET == 1) {
-        // the 128-VGPR form: the per-lane halo offsets rebuilt from an opaque lane id per chunk
-        // (kept live they spilled, and a scratch reload's vmcnt wait would drain the ring's DMA)
-        int ln = threadIdx.x & 63;
-        asm volatile("" : "+v"(ln));
-        uint32_t ho[K::HPW];
-#pragma unroll
-        for (int k = 0; k < K::HPW; ++k) ho[k] = halo_piece_off<K::HQ>(wave_id() + K::WM * k, ln, c.wp);
-        return stage_chunk_k<K::WM, K::HPW, K::WPW, K::SLOT, K::BIAS_OFF, K::HP, K::HALO_AUX>(ho, c.pstride, c.abl, s, chunk, slot,
-                                                                          with_bias, bslot);
-    }
-    return stage_chunk_k<K::WM, K::HPW, K::WPW, K::SLOT, K::BIAS_OFF, K::HP, K::HALO_AUX>(c.hoff, c.pstride, c.abl, s, chunk, slot,
-                                                                      with_bias, bslot);
-}
-
-// Interleaved refill (the pair form's one refill item issued one piece per MFMA of step 0 or, with
-// -DISR_TRUNK_INTERLEAVE=2, of step 2): OFF.  Bit-identical (tests/test_gpu_chain.py) but slower:
-// 7.41 / 7.47 ms per bench forward against 6.64 ms for the block issue, same box, two rounds each
-// (profiles/r03_trunk_interleave_ab.jsonl) — the LDS-DMA issue stalls the wave's in-order MFMA
-// stream wherever it sits, so spreading it only adds the stalls to the matrix-pipe chain.  This
-// build (python -m image_super_resolution_amd._build --interleave) passes tests/test_gpu_chain.py
-// bit for bit (round 4).  Round 3's first version also deferred EVERY staged item by one loop
-// pass and re-derived the deferred item's chunk and slot as (so - h0) / pstride and
-// (dst - smem) / SLOT; that run gave wrong 8-wave outputs and faulted the card once.  Both
-// re-derivations are exact (so = h0 + chunk * pstride with the tile offset below one plane, dst =
-// smem + slot * SLOT), the pieces stay inside a slot in both forms and push_mark's positions
-// follow the issue order, so no chunk, slot or offset of that diff can be shown out of range
-// from the code; the run was not repeated.  The bug class is closed instead: every buffer
-// resource carries its tensor's real extent (rsrc_n: an offset past it reads zeros / drops the
-// store), and the tuning build checks chunk < nch, slot < NST and the bias slot before issuing.
-// Wave priority: 1 (production) raises the wave to priority 1 around each chunk's MFMA stream
-// (s_setprio, cdna_hip_programming.md T5), so the co-resident workgroup's refill / epilogue issue
-// yields to it: 6.567 / 6.566 vs 6.620 / 6.592 ms per bench forward, same box, two rounds
-// (profiles/r03_trunk_prio_ab.jsonl); 2 (a static priority for the later-dispatched half of the
-// grid) measured no change; 0 = none.
-#ifndef ISR_TRUNK_PRIO
-#define ISR_TRUNK_PRIO 1
-#endif
-// 1: the refill's LDS-DMA issued before the step-0 fragment reads instead of after them (the DMA
-// issue is cheaper with no reads in flight, MI355X_MICROARCH.md): a tie, 6.598 / 6.598 / 6.575
-// vs 6.558 / 6.609 / 6.583 ms (profiles/r03_trunk_refill_order_ab.jsonl) — kept off.
-#ifndef ISR_TRUNK_REFILL_FIRST
-#define ISR_TRUNK_REFILL_FIRST 0
-#endif
-constexpr bool kRefillFirst = ISR_TRUNK_REFILL_FIRST != 0;
-#ifndef ISR_TRUNK_INTERLEAVE
-#define ISR_TRUNK_INTERLEAVE 0
-#endif
-constexpr bool kTrunkInterleave = ISR_TRUNK_INTERLEAVE != 0;
-// the step (dx) whose MFMAs carry the pieces: 0 (interleave 1) or 2 (interleave 2: after the
-// chunk's last LDS fragment read, so no later read of this chunk can be held behind the DMA)
-constexpr int kTrunkInterleaveStep = ISR_TRUNK_INTERLEAVE == 2 ? 2 : 0;
-
-// A refill whose LDS-DMA pieces are issued one per MFMA of the next step instead of in one block
-// before the MFMAs (a block of 7-11 LDS-DMA issues per wave ran ~1,000-2,600 cycles with the
-// matrix pipe idle: tools/trunk_items.py "reads+refill").  Same pieces, same count, same slots.
-struct Refill {
-    bool on;
-    Src src;
-    const char* xb;    // the chunk's plane base
-    uint32_t so, wo;   // in-plane halo offset of the chunk, weight offset
-    char* dst;         // slot base in LDS
-    bool bias;
-    int bslot;
-};
-
-// Piece p of this wave's share (p < HPW: halo, then weights, then the bias); p is a constant
-// once the MFMA loop it is called from is unrolled.
-template <int WM, int HPW, int WPW, int BIASB, int HP>
-__device__ __forceinline__ uint32_t refill_piece_k(const uint32_t* hoff, int abl, const Refill& rf, const int p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int wave = wave_id(), lane = threadIdx.x & 63;
-    if (p < HPW) {
-        const int j = wave + WM * p;
-        if (!(abl & 1) && j < HP) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(rf.xb, rf.src.xbytes), ISR_LDS_PTR(rf.dst + j * 1024), 16, hoff[p],
-                                                     rf.so, 0, 16);
-            return 1;
-        }
-        return 0;
-    }
-    if (p < HPW + WPW) {
-        const int j = wave + WM * (p - HPW);
-        if (j < rf.src.wpc) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(rf.src.w, rf.src.wbytes), ISR_LDS_PTR(rf.dst + (HP + j) * 1024), 16,
-                                                     lane * 16, rf.wo + j * 1024, 0, 0);
-            return 1;
-        }
-        return 0;
-    }
-    if (p == HPW + WPW && rf.bias && wave == 0) {
-        if (lane < (rf.src.wpc == tk::WPG ? 32 : 64))  // cout floats only
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(rf.src.b, rf.src.wpc == tk::WPG ? 128u : 256u), ISR_LDS_PTR(smem + BIASB + rf.bslot * 256), 4,
-                                                     lane * 4, 0, 0, 0);
-        return 1;
-    }
-    return 0;
-}
-
-template <class K>
-__device__ __forceinline__ uint32_t refill_piece(const TrunkCtx<K>& c, const Refill& rf, const int p) {
-    return refill_piece_k<K::WM, K::HPW, K::WPW, K::BIAS_OFF, K::HP>(c.hoff, c.abl, rf, p);
-}
-
-template <class K>
-__device__ __forceinline__ Refill make_refill(const TrunkCtx<K>& c, const Src& s, int chunk, int slot, bool with_bias,
-                                              int bslot) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    Refill rf;
-    rf.on = true;
-    rf.src = s;
-    rf.xb = s.x + (size_t)chunk * c.pstride;
-    rf.so = s.h0;
-    rf.wo = (uint32_t)(chunk * s.wpc * 1024);
-    rf.dst = smem + slot * K::SLOT;
-    rf.bias = with_bias;
-    rf.bslot = bslot;
-#ifdef ISR_TUNING
-    if (chunk < 0 || rf.wo >= s.wbytes || slot < 0 || slot >= K::NST || bslot < 0 || bslot > 3) {
-        if (threadIdx.x == 0) {  // as in stage_chunk: give the launch up, issue nothing
-            __hip_atomic_store(c.state + 1, c.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(c.state + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        rf.on = false;
-    }
-#endif
-    return rf;
+    return stage_pieces(c.hoff, c.pstride, c.abl, s, chunk, slot, with_bias, bslot);
 }
 
 // The tile that follows the current one in this workgroup's stream.
@@ -497,7 +346,6 @@ struct Next {
 // `issued` right after the DMA of the current item and of the items staged after it, so the
 // top of an item waits for exactly its own DMA (wait_vm(issued - m[0])) and leaves the later
 // items, stores and loads in flight.
-template <class K>
 struct Stream {
     int item;             // global index of the item being computed
     int staged;           // global index of the last item whose DMA was issued
@@ -511,8 +359,7 @@ struct Stream {
     bool dep_next;        // the next tile's neighbourhood has been verified
 };
 
-template <class K>
-__device__ __forceinline__ void push_mark(Stream<K>& st) {
+__device__ __forceinline__ void push_mark(Stream& st) {
     const int pos = st.staged - st.item;  // position of the item just staged
     const uint32_t v = st.issued;
     st.m0 = pos == 0 ? v : st.m0;
@@ -521,8 +368,7 @@ __device__ __forceinline__ void push_mark(Stream<K>& st) {
     st.m3 = pos >= 3 ? v : st.m3;
 }
 
-template <class K>
-__device__ __forceinline__ void pop_mark(Stream<K>& st) {
+__device__ __forceinline__ void pop_mark(Stream& st) {
     st.m0 = st.m1;
     st.m1 = st.m2;
     st.m2 = st.m3;
@@ -531,8 +377,7 @@ __device__ __forceinline__ void pop_mark(Stream<K>& st) {
 // Publish the pending tile's progress word now (every wave drains all its vector memory, then a
 // workgroup barrier): required before any blocking wait, so that no workgroup ever spins on a
 // word this workgroup holds back.  Wave-uniform call sites only (it contains a barrier).
-template <class K>
-__device__ __forceinline__ void force_publish(const TrunkCtx<K>& c, Stream<K>& st) {
+__device__ __forceinline__ void force_publish(const TrunkCtx& c, Stream& st) {
     if (st.pend_t < 0) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     raw_barrier();
@@ -559,19 +404,14 @@ __device__ __forceinline__ bool next_item(int L, int t, int b, int G, int ntiles
 }
 
 // Does tile t2's 3x3 neighbourhood contain tile t?
-template <class C>
-__device__ __forceinline__ bool tiles_adjacent(const C& c, int t, int t2) {
+__device__ __forceinline__ bool tiles_adjacent(const TrunkCtx& c, int t, int t2) {
     const int bx = t % c.nbx, tq = t / c.nbx, by = tq % c.nby, im = tq / c.nby;
     const int bx2 = t2 % c.nbx, nq = t2 / c.nbx, by2 = nq % c.nby, im2 = nq / c.nby;
     return im == im2 && abs(bx - bx2) <= 1 && abs(by - by2) <= 1;
 }
 
-// The production ring (2 slots, 2 fragment sets, block-issued refill) runs the forward layers'
-// tiles with the chunk stream specialised by role; every other form (deeper rings, one fragment
-// set, the interleaved refill, the masked kind-2 layers) keeps the general chunk, CR_GENERAL.
-template <class K>
-constexpr bool kChunkRoles = K::NST == 2 && K::NSET == 2 && !kTrunkInterleave;
-
+// The forward layers' tiles run the chunk stream specialised by role; the masked kind-2 layers (the
+// backward chain's gather convs) keep the general chunk, CR_GENERAL.
 enum : int {
     CR_GENERAL,  // every test at run time
     CR_FIRST,    // chunk 0: bias, counted vmcnt wait, staged at its own top when the previous tile could not
@@ -582,7 +422,7 @@ enum : int {
     CR_LAST      // refill = chunk 0 of the next item (layer kind, self-dependency, bias slot at run time)
 };
 
-// One (layer, tile).  With the chunk roles (kChunkRoles, forward layers) a steady chunk carries no
+// One (layer, tile).  With the chunk roles (forward layers) a steady chunk carries no
 // run-time generality:
 //  * its wait is the immediate vmcnt(0): its DMA was issued inside the previous chunk and the wave
 //    has issued no vector-memory instruction since (only a tile's chunk 0 has the previous tile's
@@ -602,12 +442,12 @@ enum : int {
 // Both forms keep the same stream state and hand-off protocol, so their tiles follow each other in
 // one stream, and the same MFMA, fold and epilogue order: the outputs are bit-identical.  The prep
 // kernel guarantees nch >= 4.
-template <class K, int NF, bool MASKED = false, bool H = false>
-__device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, const_rec* recs, int L, int t,
+template <int NF, bool MASKED = false, bool H = false>
+__device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_rec* recs, int L, int t,
                                          int nxL, int nxt, bool nx_exists) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int R = K::R, NST = K::NST, CT = 32 * NF, TN = 3, NA = R + 2;
-    constexpr bool ROLES = kChunkRoles<K> && !MASKED;
+    constexpr int R = TK::R, NST = TK::NST, CT = 32 * NF, TN = 3, NA = R + 2;
+    constexpr bool ROLES = !MASKED;
     // The 64-cout layers (128 accumulator + 96 fragment VGPRs) keep one chunk body per fold position
     // plus one loop body (CR_LOOP: run-time slot, run-time boundary / last test): with alternative
     // chunk bodies in the arms of a branch, or the steady run split into several loops, hipcc moves
@@ -618,7 +458,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
     const_rec& rec = recs[L];
     const int wave = wave_id(), lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
     const int bx = t % c.nbx, tmp = t / c.nbx, by = tmp % c.nby, img = tmp / c.nby;
-    const int x0 = bx * tk::TW, y0 = by * K::TH;
+    const int x0 = bx * tk::TW, y0 = by * TK::TH;
     const int nch = rec_nch(rec);
     const int first_new = rec_first_new(rec);  // NEED_NONE on layer 0
     const unsigned need = c.gen * 1024u + (unsigned)L;  // the neighbourhood is done with layer L-1
@@ -649,7 +489,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
     trunk_stamp(L, t, c.ntiles, 0);
 
     // per-lane LDS read addresses (slot 0): weights A[n][k] (n = cout), halo rows of this wave
-    const uint32_t a_w = (uint32_t)(K::HP * 1024 + (2 * l31 + (hh ^ ((l31 >> 3) & 1))) * 16);
+    const uint32_t a_w = (uint32_t)(TK::HP * 1024 + (2 * l31 + (hh ^ ((l31 >> 3) & 1))) * 16);
     uint32_t a_h[3];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
@@ -667,16 +507,16 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
     // roles: this tile's next chunk into ring slot S — the wave's share of the halo and weight
     // pieces, every piece count a constant except the ragged last round's
     auto stage_own = [&](const int sl) {
-        char* dst = smem + sl * K::SLOT;
+        char* dst = smem + sl * TK::SLOT;
         uint32_t n = 0;
         const auto rx = rsrc_n(xn, c.pstride);
         if (!(c.abl & 1)) {
 #pragma unroll
-            for (int k = 0; k < K::HPW; ++k) {
-                const int j = wave + K::WM * k;
-                if (K::WM * k + K::WM <= K::HP || j < K::HP) {
+            for (int k = 0; k < TK::HPW; ++k) {
+                const int j = wave + TK::WM * k;
+                if (TK::WM * k + TK::WM <= TK::HP || j < TK::HP) {
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ISR_LDS_PTR(dst + j * 1024), 16, c.hoff[k], me.h0, 0,
-                                                             K::HALO_AUX);
+                                                             TK::HALO_AUX);
                     ++n;
                 }
             }
@@ -684,10 +524,10 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
         if (!(c.abl & 8)) {
             const auto rw = rsrc_n(me.w, me.wbytes);
 #pragma unroll
-            for (int k = 0; k < (WPC + K::WM - 1) / K::WM; ++k) {
-                const int j = wave + K::WM * k;
-                if (K::WM * k + K::WM <= WPC || j < WPC) {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(dst + (K::HP + j) * 1024), 16, lane * 16,
+            for (int k = 0; k < (WPC + TK::WM - 1) / TK::WM; ++k) {
+                const int j = wave + TK::WM * k;
+                if (TK::WM * k + TK::WM <= WPC || j < WPC) {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(dst + (TK::HP + j) * 1024), 16, lane * 16,
                                                              wo + j * 1024, 0, 0);
                     ++n;
                 }
@@ -707,10 +547,10 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
     // S = the ring slot (roles; -1: st.item % NST at run time), ROLE = the chunk's role
     auto do_chunk = [&](const int ch, auto fc_tag, auto s_tag, auto role_tag) {
         constexpr int FC = decltype(fc_tag)::value, S = decltype(s_tag)::value, ROLE = decltype(role_tag)::value;
-        static_assert((ROLE == CR_GENERAL) == !ROLES, "roles on the production ring only");
+        static_assert((ROLE == CR_GENERAL) == MASKED, "the masked layers run the general chunk");
             const int slot = S >= 0 ? S : st.item % NST;
             const bool stamp_tile = t == (int)blockIdx.x;
-            item_stamp(L, stamp_tile, ch, 0, K::WM);
+            item_stamp(L, stamp_tile, ch, 0, TK::WM);
             // ---- top of item: this item's DMA has landed for every wave ----
             bool ring_ok = true;  // (tuning builds: the immediate wait's premise holds)
             if constexpr (ROLE == CR_FIRST) {
@@ -756,9 +596,9 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
             }
             wait_vm(st.issued - st.m0);
             }
-            item_stamp(L, stamp_tile, ch, 1, K::WM);
+            item_stamp(L, stamp_tile, ch, 1, TK::WM);
             raw_barrier();
-            item_stamp(L, stamp_tile, ch, 2, K::WM);
+            item_stamp(L, stamp_tile, ch, 2, TK::WM);
             if constexpr (ROLE == CR_GENERAL || ROLE == CR_FIRST || ROLE == CR_SECOND) {
             if (st.pend_t >= 0 && (int)(st.m0 - st.pend_mark) >= 0) {  // its stores are older than this DMA
                 if (threadIdx.x == 0)
@@ -769,7 +609,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
             if (ROLE == CR_FIRST || (ROLE == CR_GENERAL && ch == 0)) {
                 trunk_stamp(L, t, c.ntiles, 1);
                 // bias → accumulators (register g of lane l: cout (g&3) + 8(g>>2) + 4hh of fragment f)
-                const float* bs = reinterpret_cast<const float*>(smem + K::BIAS_OFF + bslot * 256);
+                const float* bs = reinterpret_cast<const float*>(smem + TK::BIAS_OFF + bslot * 256);
     #pragma unroll
                 for (int f = 0; f < NF; ++f) {
                     f32x16 b0;
@@ -783,44 +623,24 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                     for (int r = 0; r < R; ++r) acc[r][f] = b0;
                 }
             }
-            const char* sb = smem + slot * K::SLOT;
-            constexpr int NSET = K::NSET;
-            // the 1-set (128-VGPR) form rebuilds its fragment addresses from an opaque lane id at
-            // each chunk: kept live across the chunks, they were what it spilled
-            uint32_t aw = a_w, ah[3] = {a_h[0], a_h[1], a_h[2]};
-            if constexpr (NSET == 1) {
-                int ln = threadIdx.x & 63;
-                asm volatile("" : "+v"(ln));
-                const int q31 = ln & 31, qh = ln >> 5;
-                aw = (uint32_t)(K::HP * 1024 + (2 * q31 + (qh ^ ((q31 >> 3) & 1))) * 16);
-    #pragma unroll
-                for (int dx = 0; dx < 3; ++dx)
-                    ah[dx] = (uint32_t)((wave * R * tk::HC + q31 + dx) * 32 + 16 * (qh ^ (((q31 + dx) >> 3) & 1)));
-            }
-            bf16x8 fb[NSET][TN][NF], fa[NSET][NA];
+            const char* sb = smem + slot * TK::SLOT;
+            // two fragment sets: the next step's fragments are read during this step's MFMAs
+            bf16x8 fb[2][TN][NF], fa[2][NA];
             auto read_one = [&](int dx, int idx, int set) {
                 if (idx < TN * NF) {
                     const int dyi = idx / NF, f = idx % NF;
-                    fb[set][dyi][f] = lds_read16(sb + aw + ((dyi * 3 + dx) * CT * 2 + f * 64) * 16);
+                    fb[set][dyi][f] = lds_read16(sb + a_w + ((dyi * 3 + dx) * CT * 2 + f * 64) * 16);
                 } else {
                     const int ia = idx - TN * NF;
-                    fa[set][ia] = lds_read16(sb + ah[dx] + ia * tk::HC * 32);
+                    fa[set][ia] = lds_read16(sb + a_h[dx] + ia * tk::HC * 32);
                 }
             };
             auto read_fb = [&](int dx, int dyi, int set) {
     #pragma unroll
                 for (int f = 0; f < NF; ++f) read_one(dx, dyi * NF + f, set);
             };
-            // step 0's fragments in order of first use (kernel-row-major MFMA order below); with
-            // ISR_TRUNK_REFILL_FIRST the refill's LDS-DMA is issued before them instead of after
+            // step 0's fragments in order of first use (kernel-row-major MFMA order below)
             auto read_step0 = [&]() {
-                if constexpr (K::NSET == 1) {  // lazy: kernel row 0's weights and its R input rows
-                    read_fb(0, 0, 0);
-    #pragma unroll
-                    for (int ia = 0; ia < R; ++ia) read_one(0, TN * NF + ia, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    return;
-                }
                 read_fb(0, 0, 0);
     #pragma unroll
                 for (int ia = 0; ia < R; ++ia) read_one(0, TN * NF + ia, 0);
@@ -830,13 +650,10 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                 read_one(0, TN * NF + R + 1, 0);
                 __builtin_amdgcn_sched_barrier(0);
             };
-            if constexpr (!kRefillFirst) read_step0();
+            read_step0();
 
-            // ---- refill: stage the stream up to NST-1 items ahead (own chunks, then the next tile's).
-            // The last item to stage is deferred: its pieces go out one per MFMA of step 0 below
-            // (an earlier one in the same pass is issued at once, when a later one follows). ----
-            Refill rf;
-            rf.on = false;
+            // ---- refill: stage the stream one item ahead (this tile's next chunk, else the next
+            // tile's chunk 0), in one block after step 0's reads ----
             const bool last = ROLE == CR_LAST || (ROLE == CR_LOOP && ch == nch - 1);
             if constexpr (ROLE == CR_LAST || ROLE == CR_LOOP) {
                 // the next item's chunk 0 (with its bias), unless it needs this tile's own outputs
@@ -880,13 +697,6 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                         wait_deps(t, need);
                         dep_ok = true;
                     }
-                    if constexpr (kTrunkInterleave && NST == 2) {
-                        if (st.staged + 1 == st.item + NST - 1) {  // the last item of this pass: deferred
-                            rf = make_refill(c, me, off, nslot, false, 0);
-                            ++st.staged;
-                            break;
-                        }
-                    }
                     st.issued += stage_chunk(c, me, off, nslot, false, 0);
                 } else {
                     const int nc = off - nch;
@@ -896,25 +706,16 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                         wait_deps(nx.t, c.gen * 1024u + (unsigned)nx.L);
                         st.dep_next = true;
                     }
-                    if constexpr (kTrunkInterleave && NST == 2) {
-                        if (st.staged + 1 == st.item + NST - 1) {
-                            rf = make_refill(c, nx.src, nc, nslot, nc == 0, (bslot + 1) & 3);
-                            ++st.staged;
-                            break;
-                        }
-                    }
                     st.issued += stage_chunk(c, nx.src, nc, nslot, nc == 0, (bslot + 1) & 3);
                 }
                 ++st.staged;
                 push_mark(st);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (kRefillFirst) read_step0();
-            item_stamp(L, stamp_tile, ch, 3, K::WM);
-            uint32_t rf_n = 0;
-#if ISR_TRUNK_PRIO == 1
-            __builtin_amdgcn_s_setprio(1);  // the MFMA stream ahead of the partner's issue
-#endif
+            item_stamp(L, stamp_tile, ch, 3, TK::WM);
+            // the wave at priority 1 around the chunk's MFMA stream (s_setprio), so the co-resident
+            // workgroup's refill / epilogue issue yields to it
+            __builtin_amdgcn_s_setprio(1);
 
             // ---- MFMAs: 3 steps (dx), each in kernel-row-major order (dy, then output row r):
             // every accumulator still sees dy 0, 1, 2 in that order (conv3x3.hip's input-row-major
@@ -923,69 +724,33 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
             // input row ia right after the current one's last use. ----
     #pragma unroll
             for (int stp = 0; stp < 3; ++stp) {
-                const int cur = NSET == 2 ? (stp & 1) : 0;
-                if constexpr (NSET == 1) {
-                    if (stp > 0) {  // lazy: kernel row 0's weights and the first R input rows
-                        read_fb(stp, 0, 0);
-    #pragma unroll
-                        for (int ia = 0; ia < R; ++ia) read_one(stp, TN * NF + ia, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
+                const int cur = stp & 1;
     #pragma unroll
                 for (int dyi = 0; dyi < TN; ++dyi) {
-                    if constexpr (NSET == 1) {
-                        // the next kernel row's weights and its one new input row, one row ahead:
-                        // at most two kernel rows' fragments are live (the 128-VGPR budget)
-                        if (dyi + 1 < TN) {
-                            read_fb(stp, dyi + 1, 0);
-                            read_one(stp, TN * NF + dyi + R, 0);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
     #pragma unroll
                     for (int r = 0; r < R; ++r) {
-#if ISR_TRUNK_MFMA16_PROBE
-                        // timing probe (lib/libisr_probe16.so, outputs wrong): each growth-chunk
-                        // 32x32x16 MFMA replaced by two 16x16x32 of the same FLOPs on the same operands
-                        if constexpr (NF == 1) {
-                            acc[r][0] = mfma32_probe16(fb[cur][dyi][0], fa[cur][r + dyi], acc[r][0]);
-                        } else
-#endif
     #pragma unroll
                         for (int f = 0; f < NF; ++f) acc[r][f] = mfma32t<H>(fb[cur][dyi][f], fa[cur][r + dyi], acc[r][f]);
                         if constexpr (NF == 2 && FC >= 0) {
                             // residual fold: + x/s1 on the centre pixels of row r (dx = 1, dy = 1),
                             // between the row's dy = 1 and dy = 2 contributions (chunk FC, compile-time)
                             if (dyi == 1 && stp == 1) {
-                                const bf16x8 a = fold_a_bits<K::NSET == 1>(idv, FC & 1);
+                                const bf16x8 a = fold_a_bits(idv, FC & 1);
                                 acc[r][FC >> 1] = mfma32t<H>(a, fa[cur][r + 1], acc[r][FC >> 1]);
                             }
                         }
                         // input row ia = r + dyi is last used here when dyi == min(2, ia)
-                        if (NSET == 2 && stp + 1 < 3 && (dyi == 2 || r == 0))
-                            read_one(stp + 1, TN * NF + r + dyi, cur ^ 1);
-                        if (stp == kTrunkInterleaveStep && rf.on) rf_n += refill_piece<K>(c, rf, dyi * R + r);
+                        if (stp + 1 < 3 && (dyi == 2 || r == 0)) read_one(stp + 1, TN * NF + r + dyi, cur ^ 1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (NSET == 2 && stp + 1 < 3) {
+                    if (stp + 1 < 3) {
                         read_fb(stp + 1, dyi, cur ^ 1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-                if (stp == kTrunkInterleaveStep && rf.on) {
-                    // pieces beyond step 0's MFMA count (the 8-wave form), then the item's mark
-    #pragma unroll
-                    for (int q = TN * R; q <= K::HPW + K::WPW; ++q) rf_n += refill_piece<K>(c, rf, q);
-                    st.issued += rf_n;
-                    push_mark(st);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
             }
-#if ISR_TRUNK_PRIO == 1
             __builtin_amdgcn_s_setprio(0);
-#endif
-            item_stamp(L, stamp_tile, ch, 4, K::WM);
+            item_stamp(L, stamp_tile, ch, 4, TK::WM);
             pop_mark(st);  // the FIFO head moves to the next item (marks are positions from st.item)
             ++st.item;
     };
@@ -1038,17 +803,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
             }
         }
     } else {
-        int ch0 = 0;
-        if constexpr (NF == 2) {
-            if (fold && nch >= 4) {
-                do_chunk(0, TIC<0>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
-                do_chunk(1, TIC<1>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
-                do_chunk(2, TIC<2>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
-                do_chunk(3, TIC<3>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
-                ch0 = 4;
-            }
-        }
-        for (int ch = ch0; ch < nch; ++ch) do_chunk(ch, TIC<-1>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
+        for (int ch = 0; ch < nch; ++ch) do_chunk(ch, TIC<-1>{}, TIC<-1>{}, TIC<CR_GENERAL>{});
     }
     trunk_stamp(L, t, c.ntiles, 2);
 
@@ -1180,16 +935,16 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
                         }
                     }
                     if (!(c.abl & 4)) {
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tq), yr, off, 0, K::STORE_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tq), yr, off, 0, TK::STORE_AUX);
                         ++st.issued;
                     }
                 }
             }
         }
     };
-    // one wave-uniform branch per tile into the body of the layer's form (production ring only)
+    // one wave-uniform branch per tile into the body of the layer's form (the masked layers: general)
     auto epilogue_of = [&](auto form_tag) {
-        if (y0 + K::TH <= c.h && x0 + tk::TW <= c.w) epilogue(form_tag, TIC<1>{});
+        if (y0 + TK::TH <= c.h && x0 + tk::TW <= c.w) epilogue(form_tag, TIC<1>{});
         else epilogue(form_tag, TIC<0>{});
     };
     const int form = ROLES ? rec_form(rec) : (int)EPI_GENERAL;
@@ -1211,9 +966,9 @@ __device__ __forceinline__ void run_tile(const TrunkCtx<K>& c, Stream<K>& st, co
     ++st.tseq;
 }
 
-template <class K, bool H = false>
-__global__ __launch_bounds__(K::NT, K::WPS) void trunk_kernel(TrunkArgs a) {
-    TrunkCtx<K> c;
+template <bool H>
+__global__ __launch_bounds__(TK::NT, TK::WPS) void trunk_kernel(TrunkArgs a) {
+    TrunkCtx c;
     c.state = a.state;
     c.acquire = a.acquire;
     c.gen = __hip_atomic_load(a.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1240,14 +995,10 @@ __global__ __launch_bounds__(K::NT, K::WPS) void trunk_kernel(TrunkArgs a) {
     {
         const int wave = wave_id(), lane = threadIdx.x & 63;
 #pragma unroll
-        for (int k = 0; k < K::HPW; ++k) c.hoff[k] = K::NSET == 1 ? 0u : halo_piece_off<K::HQ>(wave + K::WM * k, lane, c.wp);
+        for (int k = 0; k < TK::HPW; ++k) c.hoff[k] = halo_piece_off<TK::HQ>(wave + TK::WM * k, lane, c.wp);
     }
-    const int G = gridDim.x, b = K::XM ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-#if ISR_TRUNK_PRIO == 2
-    // tuning A/B: the later-dispatched half of the grid (a CU's second workgroup) at priority 1
-    if (__builtin_amdgcn_readfirstlane(b) >= G / 2) __builtin_amdgcn_s_setprio(1);
-#endif
-    Stream<K> st;
+    const int G = gridDim.x, b = (int)blockIdx.x;
+    Stream st;
     st.item = 0;
     st.staged = 0;
     st.tseq = 0;
@@ -1266,9 +1017,9 @@ __global__ __launch_bounds__(K::NT, K::WPS) void trunk_kernel(TrunkArgs a) {
                 int nxL, nxt;
                 const bool nx_exists = next_item(L, t, b, G, c.ntiles, a.nl, nxL, nxt);
                 const int kind = rec_kind(rec);
-                if (kind == 0) run_tile<K, 1, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
-                else if (kind == 2) run_tile<K, 1, true, H>(c, st, recs, L, t, nxL, nxt, nx_exists);  // the backward chain's gathers
-                else run_tile<K, 2, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
+                if (kind == 0) run_tile<1, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
+                else if (kind == 2) run_tile<1, true, H>(c, st, recs, L, t, nxL, nxt, nx_exists);  // the backward chain's gathers
+                else run_tile<2, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
             }
         }
     }
@@ -1281,24 +1032,24 @@ __global__ __launch_bounds__(K::NT, K::WPS) void trunk_kernel(TrunkArgs a) {
 // Grid: every workgroup must be resident at once (tiles wait on other workgroups' tiles), so
 // the grid is min(tiles, resident workgroups) with residency from the occupancy API (capped at
 // what the build is made for); ISR_ERR when that is below one workgroup per CU.
-template <class K, bool H = false>
+template <bool H>
 static int trunk_launch_k(const isr_chain_desc* cd, hipStream_t s) {
-    if (cd->ha % K::TH || cd->wa % tk::TW || cd->nl < 1 || cd->nl > 1024) return -2;
-    const int nbx = cd->wa / tk::TW, nby = cd->ha / K::TH;
+    if (cd->ha % TK::TH || cd->wa % tk::TW || cd->nl < 1 || cd->nl > 1024) return -2;
+    const int nbx = cd->wa / tk::TW, nby = cd->ha / TK::TH;
     const long long ntiles = (long long)cd->n * nbx * nby;
     if (ntiles <= 0 || ntiles > (1 << 24)) return -2;
     static thread_local int cached_dev = -1, cached_per_cu = 0, cached_cus = 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
-    const void* kern = (const void*)trunk_kernel<K, H>;
+    const void* kern = (const void*)trunk_kernel<H>;
     if (dev != cached_dev) {
-        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS);
+        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, TK::LDS);
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, K::NT, K::LDS) != hipSuccess) return -1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, TK::NT, TK::LDS) != hipSuccess) return -1;
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return -1;
         cached_dev = dev;
-        cached_per_cu = per_cu < K::BPC ? per_cu : K::BPC;
+        cached_per_cu = per_cu < TK::BPC ? per_cu : TK::BPC;
         cached_cus = cus;
     }
     int per_cu = cached_per_cu;
@@ -1309,57 +1060,18 @@ static int trunk_launch_k(const isr_chain_desc* cd, hipStream_t s) {
     const long long slots = (long long)per_cu * cached_cus;
     const int grid = (int)(ntiles < slots ? ntiles : slots);
     const int rec_off = (int)trunk_rec_off((int)ntiles);
-    trunk_prep_launch(cd, K::TH, s);
+    trunk_prep_launch(cd, TK::TH, s);
     TrunkArgs a;
     a.state = cd->state;
     a.rec_off = rec_off;
     a.nl = cd->nl;
     a.acquire = cd->acquire;
-    hipLaunchKernelGGL((trunk_kernel<K, H>), dim3(grid), dim3(K::NT), K::LDS, s, a);
+    hipLaunchKernelGGL((trunk_kernel<H>), dim3(grid), dim3(TK::NT), TK::LDS, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// production: two 4-wave workgroups per CU, one chunk in flight (237 VGPRs, no scratch since
-// the RRDB residual is loaded row by row in the epilogue): 6.46 ms per bench forward against
-// 7.77 ms for the deep form (same box, tools/ab_chain.py, profiles/r03_ab_chain.jsonl) — the deep
-// form's 2-row waves read 7 LDS fragments per 6 MFMAs (4-row waves: 9 per 12)
-// ISR_TRUNK_XCD=1 (A/B build lib/libisr_xcd.so, _build.build_trunk_alt): the same form with the
-// XCD-aware tile deal (each XCD streams a contiguous range of tiles; bit-identical outputs)
-#ifndef ISR_TRUNK_XCD
-#define ISR_TRUNK_XCD 0
-#endif
-using TK_PAIR = TK<4, 4, 2, 16, ISR_TRUNK_XCD>;
-
-// The A/B forms below measured slower than the pair form on the same boxes and are
-// compiled only into the tuning library (-DISR_TUNING, lib/libisr_tuning.so): the production
-// libisr.so carries the production form alone.
-#ifdef ISR_TUNING
-using TK_DEEP = TK<8, 2, 4>;   // one 8-wave workgroup per CU, 3 chunks in flight
-// 32x32 tiles: one 8-wave workgroup per CU (4 rows per wave, as the pair form), the chunk's
-// weights staged once per CU instead of twice and a (34x34)/(32x32) halo instead of (18x34)/(16x32)
-using TK_T32 = TK<8, 4, 2, 32>;
-// the pair form's tile, ring and two workgroups per CU with 8 waves each (2 rows per wave): 4 waves
-// per SIMD at 128 VGPRs (one fragment set), and each wave issues half the refill pieces
-using TK_QUAD = TK<8, 2, 2>;
-using TK_PAIR_X = TK<4, 4, 2, 16, 1>;  // the pair form with the XCD-aware tile deal
-using TK_PAIR_NTH = TK<4, 4, 2, 16, 0, 1>;  // non-temporal halo loads
-using TK_PAIR_NTS = TK<4, 4, 2, 16, 0, 2>;  // non-temporal output stores
-// (round 6: the deep-ring form of trunk_deep.hip and the loader / consumer form of trunk_lc.hip,
-// chain variants 4 and 9, measured slower in rounds 4-5 — DESIGN.md §5 — and were removed)
-#endif
-
-int trunk_launch(const isr_chain_desc* cd, hipStream_t s, int form) {
-    if (cd->f16) return form == 0 ? trunk_launch_k<TK_PAIR, true>(cd, s) : -3;  // fp16 storage: production form only
-    if (form == 0) return trunk_launch_k<TK_PAIR>(cd, s);
-#ifdef ISR_TUNING
-    if (form == 2) return trunk_launch_k<TK_T32>(cd, s);
-    if (form == 4) return trunk_launch_k<TK_QUAD>(cd, s);
-    if (form == 5) return trunk_launch_k<TK_PAIR_X>(cd, s);
-    if (form == 6) return trunk_launch_k<TK_PAIR_NTH>(cd, s);
-    if (form == 7) return trunk_launch_k<TK_PAIR_NTS>(cd, s);
-    if (form == 1) return trunk_launch_k<TK_DEEP>(cd, s);
-#endif
-    return -3;  // an A/B form of the tuning library
+int trunk_launch(const isr_chain_desc* cd, hipStream_t s) {
+    return cd->f16 ? trunk_launch_k<true>(cd, s) : trunk_launch_k<false>(cd, s);
 }
 
 #ifdef ISR_TUNING

@@ -1,6 +1,5 @@
-// Shared pieces of the persistent RRDB-trunk kernels (trunk.hip: the two-workgroups-per-CU pair
-// form and its variants; until round 6 also trunk_deep.hip): layer records, the
-// dependency poll, buffer resources, the LDS halo image, counted vmcnt waits.
+// Shared pieces of the persistent RRDB-trunk kernel (trunk.hip): layer records, the dependency
+// poll, buffer resources, the LDS halo image, counted vmcnt waits.
 #pragma once
 #include "isr_common.h"
 
@@ -79,10 +78,8 @@ __device__ __forceinline__ int nb_of(int t, int nbx, int nby) {
 
 // s_sleep between two polls of a dependency wait (units of 64 clocks).  A spinning wave's polls
 // take issue slots from the wave computing beside it on the same SIMD (the other workgroup of the
-// CU) and draw power under the clock cap; A/B builds: _build.build_trunk_alt.
-#ifndef ISR_TRUNK_SPIN_SLEEP
-#define ISR_TRUNK_SPIN_SLEEP 1
-#endif
+// CU) and draw power under the clock cap.
+constexpr int kTrunkSpinSleep = 1;
 
 __device__ __forceinline__ unsigned poll_load(const unsigned* progress, int nb) {
     return __hip_atomic_load(progress + (nb < 0 ? 0 : nb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -105,7 +102,7 @@ __device__ __forceinline__ void dep_wait(unsigned* state, int nb, unsigned need,
             }
             break;
         }
-        __builtin_amdgcn_s_sleep(ISR_TRUNK_SPIN_SLEEP);
+        __builtin_amdgcn_s_sleep(kTrunkSpinSleep);
     }
 }
 
@@ -168,12 +165,8 @@ template <int V> struct TIC { static constexpr int value = V; };
 
 // A operand of the residual fold: (1/s1) I on couts [16 h16, 16 h16 + 16) of a 32-cout
 // fragment (lane l supplies A[l & 31][8 (l >> 5) .. + 8]); conv3x3.hip builds the same.
-template <bool FRESH = false>
 __device__ __forceinline__ bf16x8 fold_a_bits(uint32_t idv, int h16) {
-    int lane = threadIdx.x & 63;
-    // FRESH: an opaque copy of the lane id, so the operand is rebuilt at each use (a few VALU ops
-    // in the MFMA shadow) instead of being hoisted and kept live in 8 VGPRs across the chunks
-    if constexpr (FRESH) asm volatile("" : "+v"(lane));
+    const int lane = threadIdx.x & 63;
     const int j = (lane & 31) - 16 * h16 - 8 * (lane >> 5);
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     u32x4 r;
@@ -181,7 +174,6 @@ __device__ __forceinline__ bf16x8 fold_a_bits(uint32_t idv, int h16) {
     for (int d = 0; d < 4; ++d) r[d] = j == 2 * d ? idv : (j == 2 * d + 1 ? idv << 16 : 0u);
     return __builtin_bit_cast(bf16x8, r);
 }
-
 
 int trunk_prep_launch(const isr_chain_desc* cd, int th, hipStream_t s);
 

@@ -360,22 +360,11 @@ class ConvChain:
             raise ValueError("conv chain: a 16-channel activation plane must stay below 2 GiB (buffer-descriptor "
                              "window)")
         self.variant = CHAIN_VARIANT if variant is None else variant
-        if grid.f16 and (2 in kinds or self.variant != 0):
+        if self.variant != 0:
+            raise ValueError(f"conv chain: variant {self.variant} is a removed A/B form (only 0, the trunk kernel, "
+                             "exists; DESIGN.md section 5 keeps the measurements)")
+        if grid.f16 and 2 in kinds:
             raise ValueError("conv chain: fp16 storage runs the production trunk form (forward layers) only")
-        if self.variant in (3, 4) and grid.ha % 32:
-            raise ValueError(f"conv chain: variant {self.variant} (32x32 trunk tiles) needs the padded height "
-                             "a multiple of 32")
-        if self.variant == 1 and grid.t.numel() * grid.t.element_size() >= 2 ** 31:
-            # the round-2 kernel's hand-off loads / stores address a whole buffer through one
-            # descriptor with 32-bit offsets (isr_common.h rsrc_of)
-            raise ValueError("conv chain: variant 1 (the round-2 kernel) needs every activation buffer below "
-                             "2 GiB")
-        if 2 in kinds and self.variant in (1, 4):
-            raise ValueError(f"conv chain: variant {self.variant} has no masked (kind 2) layers")
-        if self.variant == 4 and any(d.cin % 32 or (k == 1 and (not d.r1.data or d.cin < 96))
-                                     for d, k in zip(descs, kinds)):
-            raise ValueError("conv chain: variant 4 pairs 16-channel chunks (cin % 32 == 0) and needs every "
-                             "64-cout layer to fold its residual r1 (cin >= 96)")
         raw = b"".join(bytes(d) for d in descs)
         self._table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
         self._kinds = torch.tensor(kinds, dtype=torch.int32, device=device)
@@ -389,11 +378,7 @@ class ConvChain:
         self.desc = ops._lib.IsrChainDesc(self._table.data_ptr(), self._kinds.data_ptr(), len(descs), grid.n,
                                           grid.ha, grid.wa, self.state.data_ptr(), int(acquire), grid.f16)
         self.nl = len(descs)
-        if self.variant == 0:
-            self.fn = lib.isr_conv_chain
-        else:
-            fv, var = lib.isr_conv_chain_variant, self.variant
-            self.fn = lambda d, s: fv(d, var, s)
+        self.fn = lib.isr_conv_chain
 
     def failed(self) -> bool:
         """True when a dependency wait gave up in the last launch (results invalid).  Synchronous
@@ -539,8 +524,7 @@ WINO_DEFAULT = wino_mode(_os.environ.get("ISR_WINO", ""))
 # invalidates L1, so it adds nothing to them and costs ~1 ms per forward on the trunk kernel
 # (per-wave fences).  Both modes are bitwise-tested (tests/test_gpu_chain.py).
 CHAIN_ACQUIRE = _os.environ.get("ISR_CHAIN_ACQUIRE", "0") == "1"
-# isr_conv_chain_variant: 0 = trunk.hip (production), 1 = the round-2 per-tile chain kernel, 2-5 the
-# A/B forms documented at isr_conv_chain_variant in include/isr.h
+# isr_conv_chain_variant id: only 0 (trunk.hip) exists; anything else raises in ConvChain
 CHAIN_VARIANT = int(_os.environ.get("ISR_CHAIN_VARIANT", "0"))
 
 

@@ -434,7 +434,7 @@ class GeneratorTrainPlan:
         # A/B option (ISR_TRAIN_RED_STREAM=1, off): the side stream's split-K reductions on a third
         # stream over a ring of RED_RING workspaces (a slot is reused once the reduce that read it
         # has finished), so the side stream chains only the weight-gradient kernels.  Skipping the
-        # reductions altogether saves 3.3 ms per cfg3 step (tuning probe, tools/r04_train_probe.sh),
+        # reductions altogether saves 3.3 ms per cfg3 step (tuning probe; script removed, see git history at f92e488),
         # but moving them off the chain loses 1.2 ms (51.7 / 51.8 vs 50.5 / 50.6 ms, alternating
         # processes, profiles/r04_train_red_stream_ab.jsonl): their cost is the partials' traffic,
         # not their place in the chain

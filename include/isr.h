@@ -369,14 +369,11 @@ int isr_conv3x3_fwd_variant(const isr_conv_desc* d, int32_t variant, isr_stream_
  * done, epilogue done [s_memrealtime, 100 MHz], -, -, HW_ID, XCC_ID); NULL stops.
  * A default build returns ISR_ERR_UNSUPPORTED. */
 int isr_tuning_conv_stamps(void* buf);
-/* Tuning builds only: per-wave stamps of later row-streaming tail launches (tail variant
- * 36 = 4 with stamps) into `buf` (4 x uint64 per (block, wave): entry, exit, summed
- * top-of-row-group wait + barrier, summed loop; s_memrealtime ticks); NULL stops. */
+/* Kept for the ABI: no shipping tail kernel writes stamps (the 4-wave walk that did was removed,
+ * DESIGN.md section 5).  Returns ISR_ERR_UNSUPPORTED in every build. */
 int isr_tuning_tail_stamps(void* buf);
-/* Tuning builds only: persistent-chain probes for later isr_conv_chain launches —
- * workgroups with bit `delay_shift` of their index set start `delay_ticks` (100 MHz) late;
- * k2 = chain kernel variant for later launches (0 = production; A/B only); k3 reserved (0).
- * A default build returns ISR_ERR_UNSUPPORTED. */
+/* Kept for the ABI: the round-2 chain kernel that read these knobs was removed (DESIGN.md
+ * section 5).  Returns ISR_ERR_UNSUPPORTED in every build. */
 int isr_tuning_chain_knobs(int32_t delay_ticks, int32_t delay_shift, int32_t k2, int32_t k3);
 /* Validation only: ISR_OK when isr_conv3x3_fwd would accept `d` (nothing launched). */
 int isr_conv3x3_check(const isr_conv_desc* d);
@@ -430,24 +427,15 @@ typedef struct isr_chain_desc {
 } isr_chain_desc;
 size_t isr_conv_chain_state_words(int32_t n, int32_t ha, int32_t wa);
 int isr_conv_chain(const isr_chain_desc* c, isr_stream_t s);
-/* The same with the kernel chosen: 0 = production (trunk.hip: one continuous K-chunk stream per
- * workgroup across its (layer, tile) items, waits only before the chunks the previous layer
- * wrote, the RDB residual folded into the MFMAs; needs every view to share (hp, wp, cs, pad),
- * a bias, cin >= 64, r1 (if any) == the layer's own input with slope 1 and 1/s1 exact in the storage type (bf16, or fp16 with f16) —
- * a table that breaks this makes the launch give up: state[1] == state[0]); 1 = the round-2
- * kernel (conv3x3.hip: one independent conv tile per (layer, tile)).  Both produce the outputs
- * of the per-layer isr_conv3x3_fwd calls bit for bit.  0 = trunk.hip in its two-workgroups-per-CU
- * form (4 waves of 4 output rows each, one K-chunk in flight); 2 = trunk.hip with one 8-wave
- * workgroup per CU (2 output rows per wave) and three chunks in flight; 3 = trunk.hip on 32x32
- * tiles, one 8-wave workgroup per CU (4 rows per wave; needs ha % 32 == 0); 5 = trunk.hip's
- * pair tile and ring with two 8-wave workgroups per CU (2 rows per wave, 4 waves per SIMD at
- * 128 VGPRs: one fragment set read a kernel row ahead, half the refill pieces per wave); 6 = the
- * production form with an XCD-aware tile deal (each XCD streams a contiguous range of tiles); 7 / 8 =
- * the production form with non-temporal halo loads / output stores.  Variants 4 (the deep-ring form,
- * round 4) and 9 (the loader / consumer form, round 5) measured slower and were removed in round 6
- * (ISR_ERR_UNSUPPORTED; their numbers stay in DESIGN.md §5).  The production library carries
- * variant 0 only (every other variant measured slower); variants 1-3 and 5-8 are
- * built into the tuning library (-DISR_TUNING) and return ISR_ERR_UNSUPPORTED here. */
+/* The same with a variant id.  Only 0 exists: trunk.hip, two 4-wave workgroups per CU (4 output
+ * rows per wave, one K-chunk in flight), one continuous K-chunk stream per workgroup across its
+ * (layer, tile) items, waits only before the chunks the previous layer wrote, the RDB residual
+ * folded into the MFMAs.  It needs every view to share (hp, wp, cs, pad), a bias, cin >= 64, and
+ * r1 (if any) == the layer's own input with slope 1 and 1/s1 exact in the storage type (bf16, or
+ * fp16 with f16); a table that breaks this makes the launch give up: state[1] == state[0].  It
+ * produces the outputs of the per-layer isr_conv3x3_fwd calls bit for bit.  Every other id (1-9
+ * were A/B forms that measured slower) returns ISR_ERR_UNSUPPORTED in every build; DESIGN.md
+ * section 5 keeps their history. */
 int isr_conv_chain_variant(const isr_chain_desc* c, int32_t variant, isr_stream_t s);
 /* Tuning builds only: per (layer 75..89, tile) stamps of later production chain launches into
  * `buf` (8 x uint64: entry, chunk 0 landed, main loop done, stores issued, deferred wait start,
@@ -465,14 +453,11 @@ int isr_tuning_trunk_item_stamps(void* buf);
 
 int isr_head9x9_fwd(const isr_head_desc* d, isr_stream_t s);
 int isr_tail9x9_fwd(const isr_tail_desc* d, isr_stream_t s);
-/* Tuning / A-B entry point: 0 = production (= 5), 1 = one 16-row tile per block, 3 = one
- * 8-row tile per block (76 KB LDS, 2 blocks / CU), 2 = persistent (one block per CU, streamed
- * halo ring), 4 = row-streaming walk down a 32-column strip (4 waves, each T row computed
- * once), 5 = the same walk with 8 waves (two per SIMD), 6 = lane-streaming walk (one wave per
- * strip, running ky sums shifted one lane per row).  All bit-identical.  The production
- * library carries 0, 3 (the fallback for outputs past 2 GiB) and 5; 1, 2, 4 and 6 are in the
- * tuning library (-DISR_TUNING) only (ISR_ERR_UNSUPPORTED here).
- * Same descriptor rules as isr_tail9x9_fwd. */
+/* The same with the kernel chosen: 0 = production (= 5), 5 = row-streaming walk down a 32-column
+ * strip with 8 waves (two per SIMD, each T row computed once), 3 = one 8-row tile per block (76 KB
+ * LDS, 2 blocks / CU; the fallback for outputs past 2 GiB).  Bit-identical.  Every other id (A/B
+ * forms that measured slower) returns ISR_ERR_UNSUPPORTED in every build; DESIGN.md section 5
+ * keeps their history.  Same descriptor rules as isr_tail9x9_fwd. */
 int isr_tail9x9_fwd_variant(const isr_tail_desc* d, int32_t variant, isr_stream_t s);
 
 /* ---- multi-tensor optimiser ops (one launch over every parameter) ---------

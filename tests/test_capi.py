@@ -94,6 +94,29 @@ def test_validation_rejects_without_touching_gpu(built_lib):
     assert lib.isr_pack_tail9x9(ctypes.c_void_p(16), ctypes.c_void_p(16), 4, 64, None) == -2
 
 
+def test_removed_ab_forms_are_refused_before_any_launch(built_lib):
+    """The A/B forms that lost against a shipping kernel were removed: chain variants 1-9 and every
+    tail id but 0, 3 and 5 return ISR_ERR_UNSUPPORTED from a descriptor that passes validation (dummy
+    non-null pointers: nothing is dereferenced or launched), and the error names the variant."""
+    lib = built_lib
+    dummy = 1 << 20  # 16-byte aligned, never dereferenced
+    c = _lib.IsrChainDesc(dummy, dummy, 5, 1, 32, 32, dummy, 0, 0)
+    for v in range(1, 10):
+        assert lib.isr_conv_chain_variant(ctypes.byref(c), v, None) == -2, v
+        err = lib.isr_last_error()
+        assert f"variant {v} ".encode() in err and b"removed" in err and b"DESIGN.md" in err, err
+    t = _lib.IsrTailDesc()
+    t.n, t.h, t.w, t.ha, t.wa, t.cin = 1, 32, 32, 32, 32, 64
+    t.x = _lib.IsrView(dummy, 40, 40, 64, 4, 0)
+    t.wpack = t.y = dummy
+    for v in (1, 2, 4, 6, 12, 36, 70, 117):
+        assert lib.isr_tail9x9_fwd_variant(ctypes.byref(t), v, None) == -2, v
+        err = lib.isr_last_error()
+        assert f"variant {v} ".encode() in err and b"removed" in err and b"DESIGN.md" in err, err
+    assert lib.isr_tuning_chain_knobs(0, 0, 0, 0) == -2 and b"removed" in lib.isr_last_error()
+    assert lib.isr_tuning_tail_stamps(None) == -2 and b"removed" in lib.isr_last_error()
+
+
 def test_packed_sizes(built_lib):
     lib = built_lib
     assert lib.isr_conv3x3_packed_bytes(64, 192) == 64 * 192 * 9 * 2

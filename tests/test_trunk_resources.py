@@ -10,7 +10,7 @@ import pytest
 
 from image_super_resolution_amd import _build
 
-PROD = re.compile(r"trunk_kernelINS_2TKILi4ELi4ELi2ELi16ELi[01]ELi0EEELb([01])EEE")
+PROD = re.compile(r"trunk_kernelILb([01])EEE")
 
 
 def _resource_lines():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Whole-image cfg4 forward (1 x 540x960 -> 2160x3840, ResNet x4) under the production plan vs
-per-conv launches (chain off) and vs tail variants: mean |diff| in LSB.  Diagnostic only."""
+per-conv launches (chain off): mean |diff| in LSB.  Diagnostic only."""
 from __future__ import annotations
 
 import ctypes

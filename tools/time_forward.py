@@ -2,7 +2,7 @@
 """Whole-forward time of the bench workload (trained x4 weights, 16 held-out 128² tiles, fp16
 default storage, HIP-graph replays, sustained: `--steps` replays per round, `--rounds` rounds) with
 whatever library ISR_LIB names; prints one JSON line with the output's checksum so alternating
-processes on two libraries can be compared (tools/r06_call22.sh: the XCD-aware trunk deal).
+processes on two libraries can be compared (script removed; see git history at f92e488).
 usage: ISR_LIB=... python tools/time_forward.py [--rounds 5 --steps 20]"""
 from __future__ import annotations
 

@@ -28,8 +28,9 @@ sys.path.insert(0, str(ROOT))
 from image_super_resolution_amd import _build  # noqa: E402
 
 CLASSES = ("mfma", "valu", "lane", "salu", "smem", "wait", "branch", "lds", "vmem")
-# production instantiations: trunk_kernel<TK<4,4,2,16,XM,0>, H> (XM = the ISR_TRUNK_XCD build option)
-PROD = re.compile(r"^_ZN3isr12trunk_kernelINS_2TKILi4ELi4ELi2ELi16ELi[01]ELi0EEELb([01])EEEvNS_9TrunkArgsE$")
+# production instantiations: trunk_kernel<H> (in a --csrc copy from before the A/B forms were removed:
+# trunk_kernel<TK<4,4,2,16,XM,0>, H>)
+PROD = re.compile(r"^_ZN3isr12trunk_kernelI(?:NS_2TKILi4ELi4ELi2ELi16ELi[01]ELi0EEE)?Lb([01])EEEvNS_9TrunkArgsE$")
 
 
 def classify(op: str) -> str | None:

@@ -3,7 +3,7 @@
 cycle stamps (s_memtime) at the item top, own DMA landed, barrier passed, refill issued and
 MFMAs issued, for layers 77 (growth2) and 79 (final) of each workgroup's first tile; prints the
 median cycles of each phase per item position, for waves 0 and WM/2.
-usage: python tools/trunk_items.py [variant 0/2]"""
+usage: python tools/trunk_items.py"""
 from __future__ import annotations
 
 import ctypes
@@ -20,7 +20,6 @@ from image_super_resolution_amd.weights import normalize, synth_lr_batch, synth_
 
 def main():
     lib = _lib.load()
-    engine.CHAIN_VARIANT = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     dev = torch.device("cuda")
     sd = synth_state_dict(models.ResNet(16, 0.2, scaleRate=4).state_dict(), seed=0)
     gw = engine.pack_generator({k: v.to(dev) for k, v in sd.items()}, enchant=False, device=dev, f16=False)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""A/B the tail9x9 kernels (isr_tail9x9_fwd_variant) on the 4x generator's tail:
+"""A/B the two tail9x9 kernels (isr_tail9x9_fwd_variant: 0 = 5, the row-streaming walk; 3, the
+8-row per-tile fallback) on the 4x generator's tail:
 16 x 64ch x 512² bf16 → 16 x 3 x 512² (fp32 and uint8 out), interleaved rounds."""
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from image_super_resolution_amd import _lib, ops  # noqa: E402
 
 lib = _lib.load()
-VS = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "1,0").split(",")]
+VS = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "3,0").split(",")]
 n, s = 16, 512
 g = torch.Generator().manual_seed(0)
 xb = ops.ActBuffer.alloc(n, s, s, 64, 4, "cuda")
