@@ -100,7 +100,14 @@ class IsrAdamArgs(ctypes.Structure):
                 ("weight_decay", c_float), ("bc2_sqrt", c_float)]
 
 
-MT_TENSOR_BYTES = 40  # isr_mt_tensor: 4 pointers + int64
+class IsrMetricsDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("border", c_int32),
+                ("a", c_void_p), ("b", c_void_p), ("a_u8", c_int32), ("b_u8", c_int32),
+                ("a_scale", c_float * 3), ("a_shift", c_float * 3), ("b_scale", c_float * 3),
+                ("b_shift", c_float * 3), ("clamp", c_int32), ("quantize", c_int32), ("out", c_void_p)]
+
+
+MT_TENSOR_BYTES = 40 # isr_mt_tensor: 4 pointers + int64
 MT_CHUNK_BYTES = 16   # isr_mt_chunk: int32 t, int32 len, int64 start
 
 
@@ -167,6 +174,8 @@ SIGNATURES = {
     "isr_mt_adam_guarded": (c_int32, [c_void_p, c_void_p, c_int32, POINTER(IsrAdamArgs), c_void_p, c_void_p,
                                       c_void_p]),
     "isr_mt_lerp_guarded": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p]),
+    "isr_image_metrics_workspace_bytes": (c_size_t, [POINTER(IsrMetricsDesc)]),
+    "isr_image_metrics": (c_int32, [POINTER(IsrMetricsDesc), c_void_p, c_size_t, c_void_p]),
     "isr_last_error": (ctypes.c_char_p, []),
     "isr_version": (c_int32, []),
 }

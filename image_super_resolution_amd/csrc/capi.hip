@@ -51,6 +51,8 @@ int mt_sumsq_dispatch(const isr_mt_tensor* ts, const isr_mt_chunk* cs, int n, fl
 int clip_coef_dispatch(const float* partial, int n, float max_norm, float* out, hipStream_t s);
 int mt_axpby_dispatch(const isr_mt_tensor* ts, const isr_mt_chunk* cs, int n, int mode, const float* coef, float d,
                       const uint32_t* guard, hipStream_t s);
+size_t image_metrics_workspace_bytes(const isr_metrics_desc* d);
+int image_metrics_dispatch(const isr_metrics_desc* d, void* ws, size_t ws_bytes, hipStream_t s);
 }  // namespace isr
 
 static thread_local char g_err[512] = "";
@@ -660,5 +662,35 @@ int isr_bn_finalize(const isr_bn_desc* d, isr_stream_t s) { return bn_run(d, 1, 
 int isr_bn_apply(const isr_bn_desc* d, isr_stream_t s) { return bn_run(d, 2, s, "bn_apply"); }
 int isr_bn_bwd_reduce(const isr_bn_desc* d, isr_stream_t s) { return bn_run(d, 3, s, "bn_bwd_reduce"); }
 int isr_bn_bwd_apply(const isr_bn_desc* d, isr_stream_t s) { return bn_run(d, 4, s, "bn_bwd_apply"); }
+
+// Nothing is launched for a refused descriptor; the size query validates the same way (out and the
+// image pointers are not needed to size the workspace, so it accepts them null).
+static int metrics_validate(const isr_metrics_desc* d, bool need_ptrs) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "image_metrics: null descriptor");
+    if (need_ptrs && (!d->a || !d->b || !d->out)) return fail(ISR_ERR_BAD_DESC, "image_metrics: null a / b / out");
+    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
+        return fail(ISR_ERR_BAD_DESC, "image_metrics: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
+    if (d->border < 0) return fail(ISR_ERR_BAD_DESC, "image_metrics: negative border %d", d->border);
+    const long long hc = (long long)d->h - 2ll * d->border, wc = (long long)d->w - 2ll * d->border;
+    if (hc < 11 || wc < 11)
+        return fail(ISR_ERR_UNSUPPORTED, "image_metrics: %dx%d less a border of %d leaves %lldx%lld, smaller than the "
+                    "11-pixel SSIM window", d->h, d->w, d->border, hc, wc);
+    return ISR_OK;
+}
+
+size_t isr_image_metrics_workspace_bytes(const isr_metrics_desc* d) {
+    if (metrics_validate(d, false) != ISR_OK) return 0;
+    return isr::image_metrics_workspace_bytes(d);
+}
+
+int isr_image_metrics(const isr_metrics_desc* d, void* workspace, size_t ws_bytes, isr_stream_t s) {
+    int rc = metrics_validate(d, true);
+    if (rc != ISR_OK) return rc;
+    if (!workspace) return fail(ISR_ERR_BAD_DESC, "image_metrics: null workspace");
+    rc = isr::image_metrics_dispatch(d, workspace, ws_bytes, (hipStream_t)s);
+    if (rc == -3) return fail(ISR_ERR_BAD_DESC, "image_metrics: workspace of %zu bytes is smaller than %zu", ws_bytes,
+                              isr::image_metrics_workspace_bytes(d));
+    return launched(rc, "image_metrics");
+}
 
 }  // extern "C"

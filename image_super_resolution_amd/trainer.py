@@ -101,6 +101,50 @@ def train(model, ema: ModelEMA, batches, transform, compute_loss, optimizer, gra
     return losses
 
 
+def validate(gen, batches, scale: int, *, mean, std, border: int = 4, group=None) -> dict:
+    """Validation pass: PSNR / PSNR-Y / SSIM-Y of `gen` (the EMA generator) on held-out HR crops.
+
+    `batches` yields uint8 HR crops [n, 3, t, t] (t a multiple of `scale`).  Each batch goes through
+    the training degradation (data.GPUTransform: the cv2 INTER_LINEAR uint8 resize, then Normalize),
+    the generator's inference path (eval mode, no autograd) and metrics.Evaluator, which compares
+    the tanh-space output with the uint8 crop on the device; the only host read is the final one.
+    The reference has no validation (its val_images.json, utils/general.py:107-111, is never read).
+    With a process group (`group`: True for the default one) image i of the stream belongs to rank
+    i % world, the sums are merged by one all-reduce and every rank returns the same dict:
+    {"psnr", "psnr_y", "ssim_y": means over images, "images": count}.  `gen`'s train / eval state
+    is restored on return."""
+    from . import data as D
+    from .metrics import Evaluator
+    g = _unwrap(gen)
+    device = next(g.parameters()).device
+    rank, world, pg = 0, 1, None
+    if group is not None:
+        import torch.distributed as dist
+        pg = None if group is True else group
+        rank, world = dist.get_rank(pg), dist.get_world_size(pg)
+    transform = D.GPUTransform(scale, hr_norm=False, mean=mean, std=std, device=device)
+    ev = Evaluator(device)
+    was_training = g.training
+    g.eval()
+    try:
+        with torch.no_grad():
+            seen = 0
+            for crops in batches:
+                first = (rank - seen) % world  # this rank's first image of the batch
+                seen += crops.shape[0]
+                mine = crops[first::world]
+                if mine.shape[0] == 0:
+                    continue
+                hr_u8 = mine.to(device, non_blocking=True).contiguous()
+                _, lr = transform(hr_u8)
+                ev.update(g(lr).float(), hr_u8, sr_space="tanh", hr_space="u8", border=border, mean=mean, std=std)
+    finally:
+        g.train(was_training)
+    if world > 1:
+        ev.all_reduce(pg)
+    return ev.result()
+
+
 def _verify(gen) -> None:
     """Epoch end: a persistent-chain give-up anywhere in the epoch raises here (engine.ChainFailed),
     before the caller logs the epoch or saves its checkpoint."""

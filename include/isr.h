@@ -510,6 +510,44 @@ int isr_mt_adam_guarded(const isr_mt_tensor* tensors, const isr_mt_chunk* chunks
 int isr_mt_lerp_guarded(const isr_mt_tensor* tensors, const isr_mt_chunk* chunks, int32_t nchunks, float d,
                         const uint32_t* guard, isr_stream_t s);
 
+/* ---- image-quality metrics ------------------------------------------------
+ * Squared error on RGB and on BT.601 luma, and SSIM on luma, of n image pairs in one pass over
+ * both inputs.  The reference computes no metric: it only defines the luma and the 4-pixel crop
+ * (Ychannel, utils/datasets.py:159-166, which nothing calls) and writes a val_images.json that
+ * nothing reads (utils/general.py:107-111); PSNR / PSNR-Y / SSIM-Y follow the literature.
+ * Each input is NCHW fp32 or uint8 with a per-channel affine into [0, 1] (uint8: 1/255, 0; tanh
+ * space [-1, 1]: 0.5, 0.5; Normalize'd: std, mean), optionally clamped to [0, 1] and quantised to
+ * the 8-bit value an image file would hold.  On the region left after cropping `border` pixels
+ * from every side (hc = h - 2*border, wc = w - 2*border), per image:
+ *   out[0] mse_rgb = mean over 3*hc*wc values of (a - b)^2
+ *   out[1] mse_y   = mean over hc*wc of (Ya - Yb)^2, Y = (65.481 r + 128.553 g + 24.966 b + 16) / 255,
+ *                    the difference formed from the channel differences (the +16 cancels)
+ *   out[2] ssim_y  = mean SSIM (Wang et al. 2004) of Y*255: 11 x 11 Gaussian window, sigma 1.5,
+ *                    normalised to sum 1, valid positions only ((hc - 10)*(wc - 10) windows, no
+ *                    padding), biased window-weighted variances, C1 = (0.01*255)^2, C2 = (0.03*255)^2
+ *   out[3]         = the number of SSIM windows
+ * all on the [0, 1] scale, so PSNR = -10 log10(mse).  Moments and sums are fp64.  When both inputs
+ * are uint8 with scale 1/255 and shift 0, mse_rgb is the exact integer sum of squares divided once
+ * by 3*hc*wc*255^2.  No atomics: block partial sums go to the caller-owned workspace
+ * (isr_image_metrics_workspace_bytes) and a second launch on the same stream adds them in a fixed
+ * order, so two calls on the same inputs give the same bits.
+ * A null pointer or n, h, w < 1 is ISR_ERR_BAD_DESC; hc < 11 or wc < 11 is ISR_ERR_UNSUPPORTED
+ * (workspace size 0); nothing is launched then. */
+typedef struct isr_metrics_desc {
+    int32_t n, h, w;        /* images, NCHW [n][3][h][w], both inputs the same shape */
+    int32_t border;         /* pixels cropped from every side before any metric (Ychannel: 4) */
+    const void* a;          /* the estimate (SR) */
+    const void* b;          /* the ground truth (HR) */
+    int32_t a_u8, b_u8;     /* 0: fp32, 1: uint8 */
+    float a_scale[3], a_shift[3];   /* value in [0,1] = v * scale[c] + shift[c] */
+    float b_scale[3], b_shift[3];
+    int32_t clamp;          /* 1: clamp both to [0,1] after the affine */
+    int32_t quantize;       /* 1: round_half_even(x*255)/255 after the clamp (the metric of the saved image) */
+    double* out;            /* [n][4]: mse_rgb, mse_y, ssim_y, valid SSIM windows (all on the [0,1] scale) */
+} isr_metrics_desc;
+size_t isr_image_metrics_workspace_bytes(const isr_metrics_desc* d);
+int isr_image_metrics(const isr_metrics_desc* d, void* workspace, size_t ws_bytes, isr_stream_t s);
+
 const char* isr_last_error(void);
 int isr_version(void);
 

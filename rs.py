@@ -10,6 +10,10 @@ dealt across ranks and rank 0 writes the image.
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 rs.py ...
 
+`--ref HR.png` (image branch) compares the written uint8 still with a ground-truth image of the
+same size on the device and prints one JSON line (psnr, psnr_y, ssim_y; `--ref_border` pixels
+cropped from every side, default 4; metrics.image_metrics).
+
 `--model` takes a checkpoint written by this package's train.py (state_dicts,
 loaded with weights_only=True) or a state_dict / .safetensors file; the
 reference's TorchScript export is not executed.
@@ -23,6 +27,7 @@ without ffmpeg.  The per-batch forward is a captured HIP graph (video.py).
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import time
 from pathlib import Path
@@ -55,6 +60,26 @@ def build_model(path: str, add_rate: float, mean, std) -> models.Model:
     m = models.Model(gen)
     m.init_normalize(mean, std)
     return m.fuse().eval()
+
+
+def read_ref(ref_path: Path, out_hw) -> torch.Tensor:
+    """The --ref image, refused before any work when it is not the size the output will have."""
+    ref = read_image(ref_path)
+    if tuple(ref.shape[1:]) != tuple(out_hw):
+        raise ValueError(f"--ref {ref_path}: the reference is {ref.shape[2]}x{ref.shape[1]} but the output will be "
+                         f"{out_hw[1]}x{out_hw[0]} (width x height)")
+    return ref
+
+
+def compare_with_ref(out: torch.Tensor, ref: torch.Tensor, ref_path: Path, border: int, device) -> dict:
+    """--ref: PSNR / PSNR-Y / SSIM-Y of the written uint8 still against a ground-truth image, on
+    the device (metrics.image_metrics with `quantize`: the values the saved file holds)."""
+    from image_super_resolution_amd import metrics
+    m = metrics.image_metrics(out.to(device), ref.to(device), sr_space="u8", hr_space="u8", border=border,
+                              quantize=True)
+    vals = torch.stack([m.psnr, m.psnr_y, m.ssim_y, m.mse, m.mse_y]).cpu()[:, 0].tolist()
+    return {"ref": ref_path.as_posix(), "border": border, "psnr": vals[0], "psnr_y": vals[1], "ssim_y": vals[2],
+            "mse": vals[3], "mse_y": vals[4]}
 
 
 def run_video(kw, device) -> None:
@@ -110,6 +135,9 @@ def runer(**kw):
                             batch=kw["batch_size"], device=device, shard=kw.get("shard", "windows"),
                             gather=kw.get("gather", "device"))
     image = read_image(src)
+    ref = None
+    if kw.get("ref"):  # every rank checks, so a refusal ends them all
+        ref = read_ref(Path(kw["ref"]), (image.shape[1] * runner.scale, image.shape[2] * runner.scale))
     if rank == 0:
         print("input shape", tuple(image.shape))
     t0 = time.perf_counter()
@@ -121,6 +149,8 @@ def runer(**kw):
         write_png(out, result)
         mpix = out.shape[1] * out.shape[2] / 1e6
         print("output shape", tuple(out.shape), result.as_posix(), f"{dt:.3f}s {mpix / dt:.1f} MPix/s")
+        if kw.get("ref"):
+            print(json.dumps(compare_with_ref(out, ref, Path(kw["ref"]), kw.get("ref_border", 4), device)))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -148,4 +178,7 @@ if __name__ == "__main__":
     p.add_argument("--wino", choices=("off", "final", "rdb"), default=None,
                    help="opt-in fp16 Winograd F(2,3) convs: the RDB final convs or all RDB convs; the trunk then "
                         "runs per conv (default off, or ISR_WINO)")
+    p.add_argument("--ref", type=str, default="", help="ground-truth image of the output's size: after the still "
+                   "is written, print one JSON line with its PSNR / PSNR-Y / SSIM-Y against it (image branch)")
+    p.add_argument("--ref_border", type=int, default=4, help="pixels cropped from every side before the metrics")
     runer(**vars(p.parse_args()))

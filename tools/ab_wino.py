@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import math
 import statistics
 import sys
 from pathlib import Path
@@ -22,7 +21,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from image_super_resolution_amd import engine, models  # noqa: E402
+from image_super_resolution_amd import engine, metrics, models  # noqa: E402
 from image_super_resolution_amd.weights import normalize, synth_lr_batch, synth_state_dict  # noqa: E402
 
 RDB_SHAPES = [(64, 32), (96, 32), (128, 32), (160, 32), (192, 64)]
@@ -30,8 +29,9 @@ RDB_SHAPES = [(64, 32), (96, 32), (128, 32), (160, 32), (192, 64)]
 
 def psnr(a: torch.Tensor, b: torch.Tensor) -> float | None:
     """PSNR in dB on the [-1, 1] output (peak 2); None when identical."""
-    mse = (a.double() - b.double()).pow(2).mean().item()
-    return None if mse == 0 else round(10 * math.log10(4.0 / mse), 2)
+    m = metrics.image_metrics(a, b, sr_space="tanh", hr_space="tanh", border=0, clamp=False)
+    mse = m.mse.mean()  # pooled over the batch, on [0, 1]: peak 1 there is peak 2 on [-1, 1]
+    return None if mse.item() == 0 else round(-10 * torch.log10(mse).item(), 2)
 
 
 def main():

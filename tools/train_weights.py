@@ -15,7 +15,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import math
 import sys
 import time
 from pathlib import Path
@@ -27,8 +26,15 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
-def psnr(a, b, peak=2.0):
-    return 10 * math.log10(peak * peak / torch.mean((a.double() - b.double()) ** 2).item())
+def batch_metrics(y_tanh, hr_u8):
+    """PSNR / PSNR-Y / SSIM-Y of a batch of tanh-space images against the uint8 HR tiles, on the device
+    (metrics.image_metrics; no border crop, as the figures this tool has always reported).  The PSNR
+    is that of the pooled error over the batch: peak 1 on [0, 1], the same number as peak 2 on [-1, 1]."""
+    from image_super_resolution_amd import metrics
+    m = metrics.image_metrics(y_tanh.float().to("cuda"), hr_u8.to("cuda"), sr_space="tanh", hr_space="u8", border=0,
+                              clamp=False)
+    return {"psnr": round(-10 * torch.log10(m.mse.mean()).item(), 3),
+            "psnr_y": round(-10 * torch.log10(m.mse_y.mean()).item(), 3), "ssim_y": round(m.ssim_y.mean().item(), 5)}
 
 
 def main():
@@ -71,11 +77,14 @@ def main():
     lr, hr = heldout_tiles(16, 128, scale=sc, device="cuda")
     with torch.no_grad():
         y = net(lr.to("cuda")).float().cpu()
-    hr1 = hr * 2 - 1
+    hr_u8 = (hr * 255.0).round().to(torch.uint8)  # the tiles are uint8 images over 255: exact
     lr01 = lr * torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1) + torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1)
     bic = F.interpolate(lr01, scale_factor=sc, mode="bicubic", align_corners=False).clamp(0, 1) * 2 - 1
+    m_hip, m_bic = batch_metrics(y, hr_u8), batch_metrics(bic, hr_u8)
     res = {"scale": sc, "hr_crop": a.shape, "train_s": round(t_train, 1), "steps": a.epochs * a.steps, "batch": a.batch,
-           "psnr_hip_vs_hr_db": round(psnr(y, hr1), 3), "psnr_bicubic_vs_hr_db": round(psnr(bic, hr1), 3)}
+           "psnr_hip_vs_hr_db": m_hip["psnr"], "psnr_bicubic_vs_hr_db": m_bic["psnr"],
+           "psnr_y_hip_vs_hr_db": m_hip["psnr_y"], "psnr_y_bicubic_vs_hr_db": m_bic["psnr_y"],
+           "ssim_y_hip_vs_hr": m_hip["ssim_y"], "ssim_y_bicubic_vs_hr": m_bic["ssim_y"]}
     # the HIP output of the first two tiles, for the CPU-side comparison against the oracle
     # (tests/diag_precision.py; tools/ never imports the oracle)
     torch.save({"y": y[:2].clone(), "lr": lr[:2].clone(), "hr": hr[:2].clone()}, (out.parent / ("trained_heldout_hip_y.pt" if sc == 4 else f"trained_heldout_hip_y_x{sc}.pt")).as_posix())

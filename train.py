@@ -10,7 +10,11 @@ as the reference; checkpoints hold state_dicts (loaded with weights_only=True),
 see checkpoint.py.  Data: `--data` takes a directory of images or a JSON list
 (the reference reads ./train_images.json); without one, or with --synthetic,
 smooth random crops are generated on the GPU.  `--steps` caps iterations per
-epoch.  Every mode trains on the HIP path: ResNet (train-mode BatchNorm kernels)
+epoch.  `--val DIR|JSON` and / or `--val_synthetic N` (with `--val_shape`, `--val_every`) validate
+the EMA generator after an epoch in `--resnet` and SRGAN mode (trainer.validate: PSNR, PSNR-Y, SSIM-Y
+on the device): one printed line, val/* scalars, a line in work_dir/val_<save_name>.jsonl, a `val`
+entry in the checkpoint and a copy of it as <checkpoint stem>.best.pt when PSNR-Y improved; without
+these flags nothing changes.  Every mode trains on the HIP path: ResNet (train-mode BatchNorm kernels)
 and EResNet (`--enchant`) in `--resnet` pixel-loss mode and in SRGAN mode (VGG
 perceptual + adversarial, discriminator on libisr), and the Denoise model
 (`--train_denoise`).
@@ -18,8 +22,11 @@ perceptual + adversarial, discriminator on libisr), and the Denoise model
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import random
+import shutil
+import time
 from copy import deepcopy
 from pathlib import Path
 
@@ -78,6 +85,84 @@ class _Batches:
                     npass += 1
             self._it = gen()
         return self._it
+
+
+def val_batches(opt, device) -> list:
+    """The validation set of --val / --val_synthetic: a list of uint8 HR batches [n, 3, S, S], built
+    once.  S = --val_shape rounded up to the scale.  --val images (a directory or a JSON list such
+    as the reference's val_images.json, utils/general.py:107-111) are centre-cropped to S; smaller
+    ones are skipped and counted.  --val_synthetic N adds N held-out dead-leaves tiles
+    (weights.heldout_tiles: seeds the training stream never uses)."""
+    side = data.ground_up(opt.val_shape, opt.scale)
+    crops = []
+    if opt.val:
+        from PIL import Image
+        skipped = 0
+        for path in data.list_images(opt.val):
+            with Image.open(path) as im:
+                a = np.asarray(im.convert("RGB"))
+            h, w = a.shape[:2]
+            if h < side or w < side:
+                skipped += 1
+                continue
+            y, x = (h - side) // 2, (w - side) // 2
+            crops.append(torch.from_numpy(np.ascontiguousarray(a[y:y + side, x:x + side])).permute(2, 0, 1))
+        print(f"Val: {len(crops)} images centre-cropped to {side}, {skipped} smaller ones skipped")
+    if opt.val_synthetic:
+        from image_super_resolution_amd.weights import heldout_tiles
+        _, hr = heldout_tiles(opt.val_synthetic, side // opt.scale, scale=opt.scale, device=device)
+        crops += list((hr * 255.0).round().to(torch.uint8))
+    if not crops:
+        raise RuntimeError(f"validation is on but no image of at least {side}x{side} was found under {opt.val!r}")
+    crops = torch.stack(crops).contiguous()
+    return list(crops.split(opt.batch_size))
+
+
+class _Validation:
+    """Validation after every --val_every-th epoch: trainer.validate on the EMA generator; rank 0
+    prints one line, logs val/* scalars, appends a JSON line to val_<save_name>.jsonl, and the
+    caller stores `entry` in the epoch's checkpoint and copies it to <stem>.best.pt when PSNR-Y
+    improved (`keep_best`)."""
+
+    def __init__(self, opt, device, work_dir: Path, rank: int, group, writer, mean, std, ck: Path):
+        self.opt, self.rank, self.group, self.writer, self.mean, self.std = opt, rank, group, writer, mean, std
+        self.batches = val_batches(opt, device)
+        self.log = work_dir / f"val_{opt.save_name}.jsonl"
+        self.best_ck = ck.with_name(ck.stem + ".best.pt")
+        self.best = float("-inf")
+        if opt.resume and rank == 0 and self.best_ck.is_file():
+            self.best = float(checkpoint.load_checkpoint(self.best_ck).get("val", {}).get("psnr_y", self.best))
+        self.entry = None
+        self.improved = False
+
+    def __call__(self, ema, epoch: int) -> None:
+        self.entry, self.improved = None, False
+        if (epoch + 1) % self.opt.val_every:
+            return
+        t0 = time.perf_counter()
+        res = trainer.validate(ema.ema, self.batches, self.opt.scale, mean=self.mean, std=self.std,
+                               group=self.group)
+        res = dict(epoch=epoch, **res, seconds=round(time.perf_counter() - t0, 4))
+        self.entry = res
+        if self.rank != 0:
+            return
+        print(f"epoch {epoch}: val psnr {res['psnr']:.3f} dB, psnr_y {res['psnr_y']:.3f} dB, "
+              f"ssim_y {res['ssim_y']:.4f} on {res['images']} images in {res['seconds']:.2f}s")
+        if self.writer is not None:
+            for k in ("psnr", "psnr_y", "ssim_y"):
+                self.writer.add_scalar(f"val/{k}", res[k], epoch)
+        with open(self.log, "a") as f:
+            f.write(json.dumps(res) + "\n")
+        if res["psnr_y"] > self.best:
+            self.best, self.improved = res["psnr_y"], True
+
+    def extra(self) -> dict:
+        """The checkpoint entry of this epoch (nothing when the epoch was not validated)."""
+        return {} if self.entry is None else {"val": self.entry}
+
+    def keep_best(self, ck: Path) -> None:
+        if self.improved:
+            shutil.copyfile(ck, self.best_ck)
 
 
 def setup_resnet(opt, device, group, iters: int, res_ck: Path):
@@ -153,6 +238,10 @@ def setup_srgan(opt, device, group, iters: int, gen_ck: Path, res_ck: Path):
 
 
 def main(opt):
+    validating = bool(opt.val or opt.val_synthetic)
+    if validating and opt.train_denoise:
+        raise ValueError("--val / --val_synthetic validate the super-resolution generators; --train_denoise has "
+                         "no validation pass")
     first_setup(opt.seed)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -225,25 +314,33 @@ def main(opt):
         model, ema, compute_loss, optimizer, schedule, start = setup_resnet(opt, device, group, iters, res_ck)
         print(f"Train: ResNet {opt.epochs} epochs, {sum(p.numel() for p in model.parameters()):,} parameters")
         transform = data.GPUTransform(opt.scale, hr_norm=False, mean=mean, std=std, device=device)
+        val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, res_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train(model, ema, batches, transform, compute_loss, optimizer, scaler_gen, schedule,
                                    epoch, writer, steps=iters)
+            if val is not None:
+                val(ema, epoch)
             if rank == 0:
                 print(f"epoch {epoch}: loss {np.mean(losses):.5f}")
                 checkpoint.save_checkpoint(res_ck, gen_net=model, optimizer=optimizer.state_dict()
                                            if epoch != opt.epochs - 1 else None, epoch=epoch, mean=mean, std=std,
                                            loss=losses, scaler=scaler_gen.state_dict(), ema=ema.ema,
-                                           updates=ema.updates)
+                                           updates=ema.updates, **(val.extra() if val is not None else {}))
+                if val is not None:
+                    val.keep_best(res_ck)
     else:
         gen_net, dis_net, ema, optimizer_g, optimizer_d, schedule_g, schedule_d, compute_loss, start = \
             setup_srgan(opt, device, group, iters, gen_ck, res_ck)
         print(f"Train: {opt.epochs} epochs, gen {sum(p.numel() for p in gen_net.parameters()):,} parameters, "
               f"dis {sum(p.numel() for p in dis_net.parameters()):,} parameters")
         transform = data.GPUTransform(opt.scale, hr_norm=True, mean=mean, std=std, device=device)
+        val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, gen_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train_srgan(gen_net, ema, dis_net, batches, transform, compute_loss, optimizer_g,
                                          optimizer_d, (scaler_gen, scaler_dis), (schedule_g, schedule_d), epoch,
                                          writer, mean=mean, std=std, steps=iters, dist_group=group)
+            if val is not None:
+                val(ema, epoch)
             if rank == 0:
                 print(f"epoch {epoch}: content loss {np.mean(losses):.5f}")
                 checkpoint.save_checkpoint(gen_ck, gen_net=gen_net, dis_net=dis_net,
@@ -251,7 +348,10 @@ def main(opt):
                                            optimizer_d=optimizer_d.state_dict() if epoch != opt.epochs - 1 else None,
                                            mean=mean, std=std, loss=losses, epoch=epoch,
                                            scaler_gen=scaler_dis.state_dict(), scaler_res=scaler_gen.state_dict(),
-                                           ema=ema.ema, updates=ema.updates)
+                                           ema=ema.ema, updates=ema.updates,
+                                           **(val.extra() if val is not None else {}))
+                if val is not None:
+                    val.keep_best(gen_ck)
     if writer is not None:
         writer.close()
     if world > 1:
@@ -296,7 +396,15 @@ def parse(argv=None):
     p.add_argument("--vgg_weights", type=str, default=None)
     p.add_argument("--dis_miopen", action="store_true", help="run the discriminator's conv stack on stock MIOpen "
                    "convs (NHWC + find mode) instead of libisr")
+    p.add_argument("--val", type=str, default="", help="validation images: a directory or a JSON list (e.g. the "
+                   "reference's val_images.json); PSNR / PSNR-Y / SSIM-Y of the EMA generator after an epoch")
+    p.add_argument("--val_synthetic", type=int, default=0, help="validate on N held-out dead-leaves tiles (no files)")
+    p.add_argument("--val_shape", type=int, default=512, help="HR centre crop of the validation images (rounded up "
+                   "to the scale; smaller images are skipped)")
+    p.add_argument("--val_every", type=int, default=1, help="validate after every E-th epoch")
     opt = p.parse_args(argv)
+    if opt.val_every < 1:
+        p.error("--val_every must be at least 1")
     if not opt.data and Path("train_images.json").is_file():
         opt.data = "train_images.json"
     if opt.steps == 0:
