@@ -107,6 +107,22 @@ class IsrMetricsDesc(ctypes.Structure):
                 ("b_shift", c_float * 3), ("clamp", c_int32), ("quantize", c_int32), ("out", c_void_p)]
 
 
+class IsrJpegDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("src", c_void_p), ("dst", c_void_p),
+                ("quality", c_void_p)]
+
+
+class IsrHlsMomentsDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("src", c_void_p), ("out", c_void_p),
+                ("partials", c_void_p)]
+
+
+class IsrIsoNoiseDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("src", c_void_p), ("dst", c_void_p),
+                ("lum_noise", c_void_p), ("hue_noise", c_void_p), ("apply", c_void_p)]
+
+
+HLS_PARTIAL_BLOCKS = 32  # ISR_HLS_PARTIAL_BLOCKS
 MT_TENSOR_BYTES = 40 # isr_mt_tensor: 4 pointers + int64
 MT_CHUNK_BYTES = 16   # isr_mt_chunk: int32 t, int32 len, int64 start
 
@@ -176,6 +192,10 @@ SIGNATURES = {
     "isr_mt_lerp_guarded": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p]),
     "isr_image_metrics_workspace_bytes": (c_size_t, [POINTER(IsrMetricsDesc)]),
     "isr_image_metrics": (c_int32, [POINTER(IsrMetricsDesc), c_void_p, c_size_t, c_void_p]),
+    "isr_jpeg_roundtrip_workspace_bytes": (c_size_t, [POINTER(IsrJpegDesc)]),
+    "isr_jpeg_roundtrip": (c_int32, [POINTER(IsrJpegDesc), c_void_p, c_size_t, c_void_p]),
+    "isr_hls_l_moments": (c_int32, [POINTER(IsrHlsMomentsDesc), c_void_p]),
+    "isr_iso_noise": (c_int32, [POINTER(IsrIsoNoiseDesc), c_void_p]),
     "isr_last_error": (ctypes.c_char_p, []),
     "isr_version": (c_int32, []),
 }

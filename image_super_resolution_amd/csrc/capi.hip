@@ -53,6 +53,10 @@ int mt_axpby_dispatch(const isr_mt_tensor* ts, const isr_mt_chunk* cs, int n, in
                       const uint32_t* guard, hipStream_t s);
 size_t image_metrics_workspace_bytes(const isr_metrics_desc* d);
 int image_metrics_dispatch(const isr_metrics_desc* d, void* ws, size_t ws_bytes, hipStream_t s);
+size_t jpeg_roundtrip_workspace_bytes(const isr_jpeg_desc* d);
+int jpeg_roundtrip_dispatch(const isr_jpeg_desc* d, void* ws, size_t ws_bytes, hipStream_t s);
+int hls_l_moments_dispatch(const isr_hls_moments_desc* d, hipStream_t s);
+int iso_noise_dispatch(const isr_iso_noise_desc* d, hipStream_t s);
 }  // namespace isr
 
 static thread_local char g_err[512] = "";
@@ -691,6 +695,64 @@ int isr_image_metrics(const isr_metrics_desc* d, void* workspace, size_t ws_byte
     if (rc == -3) return fail(ISR_ERR_BAD_DESC, "image_metrics: workspace of %zu bytes is smaller than %zu", ws_bytes,
                               isr::image_metrics_workspace_bytes(d));
     return launched(rc, "image_metrics");
+}
+
+// ---- training-data degradations (degrade.hip) ----
+
+static int jpeg_validate(const isr_jpeg_desc* d, bool need_ptrs) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: null descriptor");
+    if (need_ptrs && (!d->src || !d->dst || !d->quality))
+        return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: null src / dst / quality");
+    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
+        return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
+    if (d->h % 16 || d->w % 16)
+        return fail(ISR_ERR_UNSUPPORTED, "jpeg_roundtrip: %dx%d is not whole 4:2:0 MCUs: h and w must be multiples "
+                    "of 16", d->h, d->w);
+    if ((long long)d->n * 3 * d->h * d->w >= (1ll << 31))
+        return fail(ISR_ERR_UNSUPPORTED, "jpeg_roundtrip: n*3*h*w = %lld does not fit 31 bits",
+                    (long long)d->n * 3 * d->h * d->w);
+    if (need_ptrs && (((uintptr_t)d->src | (uintptr_t)d->dst) % 16 || (uintptr_t)d->quality % 4))
+        return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: src and dst must be 16-byte aligned, quality 4-byte aligned");
+    return ISR_OK;
+}
+
+size_t isr_jpeg_roundtrip_workspace_bytes(const isr_jpeg_desc* d) {
+    if (jpeg_validate(d, false) != ISR_OK) return 0;
+    return isr::jpeg_roundtrip_workspace_bytes(d);
+}
+
+int isr_jpeg_roundtrip(const isr_jpeg_desc* d, void* workspace, size_t ws_bytes, isr_stream_t s) {
+    int rc = jpeg_validate(d, true);
+    if (rc != ISR_OK) return rc;
+    if (!workspace || (uintptr_t)workspace % 16)
+        return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: null or not 16-byte aligned workspace");
+    rc = isr::jpeg_roundtrip_dispatch(d, workspace, ws_bytes, (hipStream_t)s);
+    if (rc == -3) return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: workspace of %zu bytes is smaller than %zu", ws_bytes,
+                              isr::jpeg_roundtrip_workspace_bytes(d));
+    return launched(rc, "jpeg_roundtrip");
+}
+
+int isr_hls_l_moments(const isr_hls_moments_desc* d, isr_stream_t s) {
+    if (!d || !d->src || !d->out || !d->partials)
+        return fail(ISR_ERR_BAD_DESC, "hls_l_moments: null descriptor / src / out / partials");
+    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
+        return fail(ISR_ERR_BAD_DESC, "hls_l_moments: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
+    if ((uintptr_t)d->out % 8 || (uintptr_t)d->partials % 8)
+        return fail(ISR_ERR_BAD_DESC, "hls_l_moments: out and partials must be 8-byte aligned");
+    return launched(isr::hls_l_moments_dispatch(d, (hipStream_t)s), "hls_l_moments");
+}
+
+int isr_iso_noise(const isr_iso_noise_desc* d, isr_stream_t s) {
+    if (!d || !d->src || !d->dst || !d->lum_noise || !d->hue_noise || !d->apply)
+        return fail(ISR_ERR_BAD_DESC, "iso_noise: null descriptor / src / dst / lum_noise / hue_noise / apply");
+    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
+        return fail(ISR_ERR_BAD_DESC, "iso_noise: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
+    if (((uintptr_t)d->lum_noise | (uintptr_t)d->hue_noise | (uintptr_t)d->apply) % 4)
+        return fail(ISR_ERR_BAD_DESC, "iso_noise: lum_noise, hue_noise and apply must be 4-byte aligned");
+    const long long hw = (long long)d->h * d->w;
+    if ((hw + 255) / 256 >= (1ll << 31))
+        return fail(ISR_ERR_UNSUPPORTED, "iso_noise: %dx%d needs more than 2^31 - 1 workgroups per image", d->h, d->w);
+    return launched(isr::iso_noise_dispatch(d, (hipStream_t)s), "iso_noise");
 }
 
 }  // extern "C"

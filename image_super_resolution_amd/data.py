@@ -124,17 +124,44 @@ class GPUTransform:
 class NoisyTransform:
     """Batched (clean, noisy) pairs for `train.py --train_denoise` from uint8 crops
     on the device (Noisy_dataset, utils/datasets.py:361-389): clean = 2*crop/255 - 1;
-    noisy = Normalize(GaussNoise(crop)), albumentations GaussNoise defaults
-    (var_limit (10, 50) on the 0-255 scale, per-channel, p = 0.5 per sample, result
-    clipped to [0, 255]).  The reference's ISONoise and ImageCompression (also p = 0.5)
-    need a host JPEG codec / HLS conversion and are not reproduced."""
+    noisy = Normalize(ImageCompression(ISONoise(GaussNoise(crop)))), each stage applied per
+    sample with its own probability:
+
+    * GaussNoise, albumentations defaults: var_limit (10, 50) on the 0-255 scale, per channel,
+      probability `p`, result clipped to [0, 255];
+    * ISONoise (probability `iso_p`): Poisson luminance and Gaussian hue noise in HLS space,
+      color_shift and intensity uniform in `iso_color_shift` / `iso_intensity`
+      (degrade.iso_noise, libisr's isr_hls_l_moments + isr_iso_noise);
+    * ImageCompression (probability `jpeg_p`): a JPEG round trip at an integer quality uniform
+      in the inclusive `jpeg_quality` range (degrade.jpeg_roundtrip, libisr's isr_jpeg_roundtrip).
+
+    With iso_p = jpeg_p = 0 (the default) only GaussNoise runs, in float, and the output and the
+    generator's draws are what they were before the other stages existed.  With either on, the
+    stages exchange uint8 images as the reference's do (GaussNoise's result is truncated to
+    uint8), the extra draws follow the three GaussNoise draws, and the stages are HIP kernels:
+    a CPU device raises.  `NoisyTransform.reference(...)` is the reference's pipeline
+    (iso_p = jpeg_p = 0.5)."""
 
     def __init__(self, mean=IMAGENET_MEAN, std=IMAGENET_STD, var_limit=(10.0, 50.0), p: float = 0.5,
-                 device="cuda", seed: int = 0):
+                 device="cuda", seed: int = 0, iso_p: float = 0.0, jpeg_p: float = 0.0, jpeg_quality=(50, 75),
+                 iso_color_shift=(0.01, 0.05), iso_intensity=(0.1, 0.5)):
         self.mean = torch.tensor(mean, device=device).view(1, 3, 1, 1)
         self.std = torch.tensor(std, device=device).view(1, 3, 1, 1)
         self.var_limit, self.p, self.device = var_limit, p, device
+        self.iso_p, self.jpeg_p = float(iso_p), float(jpeg_p)
+        self.jpeg_quality, self.iso_color_shift, self.iso_intensity = jpeg_quality, iso_color_shift, iso_intensity
+        lo, hi = jpeg_quality
+        if int(lo) != lo or int(hi) != hi or not 1 <= lo <= hi <= 100:
+            raise ValueError(f"NoisyTransform: jpeg quality range must be integers with 1 <= lower <= upper <= 100, "
+                             f"got {jpeg_quality}")
         self.gen = torch.Generator(device=device).manual_seed(seed)
+
+    @classmethod
+    def reference(cls, *args, **kw):
+        """The reference's Noisy_dataset pipeline: all three stages at p = 0.5."""
+        kw.setdefault("iso_p", 0.5)
+        kw.setdefault("jpeg_p", 0.5)
+        return cls(*args, **kw)
 
     def __call__(self, crops_u8: torch.Tensor):
         x = crops_u8.to(self.device, non_blocking=True).float()
@@ -143,10 +170,32 @@ class NoisyTransform:
         var = torch.empty(n, 1, 1, 1, device=self.device).uniform_(*self.var_limit, generator=g)
         apply = (torch.rand(n, 1, 1, 1, device=self.device, generator=g) < self.p).float()
         noise = torch.randn(x.shape, device=self.device, generator=g) * var.sqrt() * apply
-        noisy = (x + noise).clamp_(0, 255).div_(255.0)
-        lr = (noisy - self.mean) / self.std
         hr = x / 255.0 * 2.0 - 1.0
+        if self.iso_p > 0 or self.jpeg_p > 0:
+            noisy = self._degrade((x + noise).clamp_(0, 255).to(torch.uint8)).float().div_(255.0)
+        else:
+            noisy = (x + noise).clamp_(0, 255).div_(255.0)
+        lr = (noisy - self.mean) / self.std
         return hr.contiguous(), lr.contiguous()
+
+    def _degrade(self, u8: torch.Tensor) -> torch.Tensor:
+        """ISONoise and the JPEG round trip on the uint8 result of GaussNoise (HIP only)."""
+        from . import degrade
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("NoisyTransform: the ISONoise and JPEG stages are HIP kernels (MI355X only); "
+                               f"device {self.device!r} has no such path (there is no host fallback)")
+        n, g = u8.shape[0], self.gen
+        if self.iso_p > 0:
+            on = torch.rand(n, device=self.device, generator=g) < self.iso_p
+            cs = torch.empty(n, device=self.device).uniform_(*self.iso_color_shift, generator=g)
+            it = torch.empty(n, device=self.device).uniform_(*self.iso_intensity, generator=g)
+            u8 = degrade.iso_noise(u8, cs, it, g, apply=on)
+        if self.jpeg_p > 0:
+            on = torch.rand(n, device=self.device, generator=g) < self.jpeg_p
+            lo, hi = self.jpeg_quality
+            q = torch.randint(int(lo), int(hi) + 1, (n,), device=self.device, generator=g, dtype=torch.int32)
+            u8 = degrade.jpeg_roundtrip(u8, q * on.to(torch.int32))
+        return u8
 
 
 NATURAL_ALPHA = 1.4  # amplitude spectrum 1/f^alpha: x4 bicubic PSNR ~27.7 dB, the regime of COCO crops

@@ -548,6 +548,78 @@ typedef struct isr_metrics_desc {
 size_t isr_image_metrics_workspace_bytes(const isr_metrics_desc* d);
 int isr_image_metrics(const isr_metrics_desc* d, void* workspace, size_t ws_bytes, isr_stream_t s);
 
+/* ---- training-data degradations ---------------------------------------------
+ * The second and third stage of the reference's Noisy_dataset (utils/datasets.py:374-377:
+ * albumentations ISONoise and ImageCompression after GaussNoise), on uint8 crops that are already
+ * on the device.  Every image is contiguous planar uint8 [n][3][h][w], RGB.  A null pointer or
+ * n, h, w < 1 is ISR_ERR_BAD_DESC, an unsupported shape ISR_ERR_UNSUPPORTED; nothing is launched
+ * then.  dst may be src.
+ *
+ * isr_jpeg_roundtrip: the decoded pixels of a baseline 4:2:0 JPEG of each image at quality[i]
+ * (a device array; 1..100, 0 copies the image through unchanged, which is how a per-sample
+ * probability is applied without a host sync; values above 100 act as 100, below 0 as 0).
+ * Arithmetic as libjpeg: encode = JFIF RGB->YCbCr in 16-bit fixed point, h2v2 chroma downsample
+ * ((sum of four + bias 1, 2, 1, 2, ...) >> 2), level shift, 8x8 DCT-II (fp32), IJG base tables
+ * scaled by s = q < 50 ? 5000/q : 200 - 2q as clamp((base*s + 50)/100, 1, 255), quantised rounding
+ * half away from zero; decode = dequantise, IDCT (fp32), + 128, round, clamp, h2v2 "fancy" triangle
+ * upsample of the chroma planes (3:1 vertically then horizontally, biases 8 / 7, >> 4, edges
+ * replicated at the component border, across MCU borders), fixed-point YCbCr->RGB, clamp.  The
+ * coefficients (u, v) in {0, 4}^2 are integer sums / 8 and are carried as integers through both
+ * transforms, so a flat region's quantisation ties round the same way on every run.  libjpeg's
+ * integer DCT differs from the fp32 one by a few flipped coefficients.
+ * h and w must be multiples of 16 (whole MCUs; otherwise ISR_ERR_UNSUPPORTED), src, dst and the
+ * workspace 16-byte aligned, n*3*h*w < 2^31, n <= 65535.  Two launches on `s`; the workspace
+ * (isr_jpeg_roundtrip_workspace_bytes, n*h*w*3/2) holds Y, Cb and Cr between them. */
+typedef struct isr_jpeg_desc {
+    int32_t n, h, w;
+    const uint8_t* src;
+    uint8_t* dst;
+    const int32_t* quality; /* device, [n] */
+} isr_jpeg_desc;
+size_t isr_jpeg_roundtrip_workspace_bytes(const isr_jpeg_desc* d);
+int isr_jpeg_roundtrip(const isr_jpeg_desc* d, void* workspace, size_t ws_bytes, isr_stream_t s);
+
+/* isr_hls_l_moments: per image the mean and the population standard deviation of the HLS
+ * lightness L = (max(r,g,b) + min(r,g,b)) / 2 on the [0, 1] scale (cv2.meanStdDev of the L plane),
+ * out[i] = {mean, std}.  max + min is an integer <= 510: its sum and sum of squares are
+ * accumulated as 64-bit integers (block partials in the caller-owned `partials`, added by a second
+ * launch; no atomics), N*S2 - S1^2 is formed in 128 bits and divided once, so the result is exact
+ * to fp64 rounding and the same on every call; a flat image has std == 0 exactly.  Any h, w >= 1;
+ * n <= 65535. */
+#define ISR_HLS_PARTIAL_BLOCKS 32
+typedef struct isr_hls_moments_desc {
+    int32_t n, h, w;
+    const uint8_t* src;
+    double* out;        /* [n][2] */
+    uint64_t* partials; /* scratch, [n][ISR_HLS_PARTIAL_BLOCKS][2] */
+} isr_hls_moments_desc;
+int isr_hls_l_moments(const isr_hls_moments_desc* d, isr_stream_t s);
+
+/* isr_iso_noise: albumentations' ISONoise given its two noise planes.  Per pixel of an image
+ * with apply[i] != 0 (apply[i] == 0 copies it through), in fp32, one rounding per operation:
+ *   r, g, b = src / 255;  vmax, vmin;  sm = vmax + vmin;  d = vmax - vmin;  L = sm * 0.5
+ *   d == 0: H = S = 0;  else S = L < 0.5 ? d / sm : d / (2 - sm),  k = 60 / d,
+ *           H = (g-b)k | (b-r)k + 120 | (r-g)k + 240 for vmax == r | g | b,  H < 0: H += 360
+ *   H += hue_noise;  H < 0: H += 360;  H > 360: H -= 360
+ *   L = L + (lum_noise / 255) * (1 - L)
+ *   S == 0: r = g = b = L;  else p2 = L <= 0.5 ? L(1 + S) : (L + S) - L*S,  p1 = 2L - p2,
+ *           hh = H * (1/60);  hh -= 6 floor(hh * (1/6));  sector = clamp(floor(hh), 0, 5);
+ *           f = hh - sector;  fall = p1 + (p2-p1)(1-f);  rise = p1 + (p2-p1)f;
+ *           (r, g, b) = (p2,rise,p1) (fall,p2,p1) (p1,p2,rise) (p1,fall,p2) (rise,p1,p2) (p2,p1,fall)
+ *   dst = (uint8) trunc(clamp(255 * (r, g, b), 0, 255))
+ * lum_noise (Poisson counts) and hue_noise (degrees) are fp32 [n][h][w].  This formula is the
+ * contract: it restates the published albumentations / OpenCV arithmetic and is not pinned against
+ * either library.  Any h, w >= 1; n <= 65535. */
+typedef struct isr_iso_noise_desc {
+    int32_t n, h, w;
+    const uint8_t* src;
+    uint8_t* dst;
+    const float* lum_noise;
+    const float* hue_noise;
+    const int32_t* apply; /* device, [n] */
+} isr_iso_noise_desc;
+int isr_iso_noise(const isr_iso_noise_desc* d, isr_stream_t s);
+
 const char* isr_last_error(void);
 int isr_version(void);
 

@@ -300,7 +300,13 @@ def main(opt):
         schedule = torch.optim.lr_scheduler.LinearLR(optimizer, 1, opt.lr2, total_iters=opt.epochs * iters)
         n_p = sum(p.numel() for p in model.parameters())
         print(f"Model: {n_p:,} parameters, {n_p:,} gradients")
-        transform = data.NoisyTransform(mean, std, device=device, seed=opt.seed * 7 + rank)
+        # ISR_DENOISE_DEGRADE=reference: the reference's three-stage pipeline (GaussNoise, ISONoise, JPEG at
+        # p = 0.5 each) instead of GaussNoise alone; an environment opt-in, as ISR_WINO is
+        degrade_mode = os.environ.get("ISR_DENOISE_DEGRADE", "")
+        if degrade_mode not in ("", "gauss", "reference"):
+            raise ValueError(f"ISR_DENOISE_DEGRADE={degrade_mode!r}: '' / 'gauss' (GaussNoise only) or 'reference'")
+        make_transform = data.NoisyTransform.reference if degrade_mode == "reference" else data.NoisyTransform
+        transform = make_transform(mean, std, device=device, seed=opt.seed * 7 + rank)
         for epoch in range(start, opt.epochs):
             losses = trainer.train(model, ema, batches, transform, nn.MSELoss(), optimizer, scaler_gen, schedule,
                                    epoch, writer, steps=iters)
