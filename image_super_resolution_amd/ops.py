@@ -493,10 +493,18 @@ def wgrad9x9(p: torch.Tensor, q: ActBuffer, dw: torch.Tensor, db: torch.Tensor |
     launch_wgrad9x9(wgrad9x9_desc(p, q, dw, db, **kw), p.device)
 
 
+def _bf16_only(what: str, *bufs) -> None:
+    """The elementwise / layout / pool / BatchNorm kernels read and write bf16 (load8_bf16 /
+    store8_bf16): refuse an fp16 ActBuffer instead of reinterpreting its bits."""
+    if any(b is not None and b.f16 for b in bufs):
+        raise TypeError(f"{what}: the kernel is bf16 only, got a torch.float16 ActBuffer")
+
+
 def ew_combine_desc(y: ActBuffer, a: ActBuffer, c: int, *, sa: float = 1.0, b: ActBuffer | None = None,
                     sb: float = 1.0, m: ActBuffer | None = None, mslope: float = 1.0,
                     y_coff: int = 0, a_coff: int = 0, b_coff: int = 0, m_coff: int = 0) -> IsrEwDesc:
     """y = (a*sa + b*sb) * LeakyReLU'(m) over c channels (zero outside the valid region)."""
+    _bf16_only("ew_combine_desc", y, a, b, m)
     d = IsrEwDesc()
     d.n, d.h, d.w, d.ha, d.wa, d.c = y.n, y.h, y.w, y.ha, y.wa, c
     d.y, d.a = y.view(y_coff), a.view(a_coff)
@@ -512,6 +520,7 @@ def ew_combine(y: ActBuffer, a: ActBuffer, c: int, **kw) -> None:
 
 def pixel_shuffle2_desc(y: ActBuffer, a: ActBuffer, c: int, *, slope: float = 1.0, sa: float = 1.0) -> IsrEwDesc:
     """y[0:c] (grid 2h x 2w) = LeakyReLU_slope(sa * PixelShuffle(2)(a[0:4c]))."""
+    _bf16_only("pixel_shuffle2_desc", y, a)
     d = IsrEwDesc()
     d.n, d.h, d.w, d.ha, d.wa, d.c = y.n, y.h, y.w, y.ha, y.wa, c
     d.y, d.a, d.b, d.m = y.view(0), a.view(0), _NULL_VIEW, _NULL_VIEW
@@ -522,6 +531,7 @@ def pixel_shuffle2_desc(y: ActBuffer, a: ActBuffer, c: int, *, slope: float = 1.
 def pixel_unshuffle2_desc(y: ActBuffer, a: ActBuffer, c: int, *, m: ActBuffer | None = None, mslope: float = 1.0,
                           sa: float = 1.0) -> IsrEwDesc:
     """y[0:c] (grid h x w) = PixelShuffle(2)ᵀ(sa * a[0:c/4] * LeakyReLU'(m)) — a, m on the 2h x 2w grid."""
+    _bf16_only("pixel_unshuffle2_desc", y, a, m)
     d = IsrEwDesc()
     d.n, d.h, d.w, d.ha, d.wa, d.c = y.n, y.h, y.w, y.ha, y.wa, c
     d.y, d.a, d.b = y.view(0), a.view(0), _NULL_VIEW
@@ -543,6 +553,7 @@ def pixel_shuffle2(y: ActBuffer, a: ActBuffer, c: int, **kw) -> None:
 def convert_desc(nchw: torch.Tensor, v: ActBuffer, *, v_coff: int = 0, scale: torch.Tensor | None = None,
                  shift: torch.Tensor | None = None, m: ActBuffer | None = None, mslope: float = 1.0,
                  m_coff: int = 0) -> IsrConvertDesc:
+    _bf16_only("convert_desc", v, m)
     _require_gpu(nchw, "convert")
     if nchw.dtype != torch.float32 or not nchw.is_contiguous() or nchw.dim() != 4:
         raise ValueError("convert: nchw must be contiguous fp32 [n, c, h, w]")
@@ -570,6 +581,7 @@ def blocked_to_nchw(v: ActBuffer, out: torch.Tensor, **kw) -> torch.Tensor:
 
 
 def pool_desc(x: ActBuffer, y: ActBuffer, c: int, g: ActBuffer | None = None, mslope: float = 0.0) -> IsrPoolDesc:
+    _bf16_only("pool_desc", x, y, g)
     if (y.h, y.w) != (x.h // 2, x.w // 2) or y.ha * 2 > x.ha or y.wa * 2 > x.wa:
         raise ValueError("maxpool2: output grid must be (h/2, w/2) with 2*ha_out within the input buffer")
     d = IsrPoolDesc()
@@ -604,6 +616,7 @@ def bn_desc(z: ActBuffer, y: ActBuffer, c: int, st: BNState, bn: "torch.nn.Batch
             r2: ActBuffer | None = None, r2_coff: int = 0, s2: float = 1.0, dz: ActBuffer | None = None,
             dz_coff: int = 0, dgamma: torch.Tensor | None = None, dbeta: torch.Tensor | None = None,
             gscale: float = 1.0, update_running: bool = True) -> _lib.IsrBnDesc:
+    _bf16_only("bn_desc", z, y, r1, r2, dz)
     d = _lib.IsrBnDesc()
     d.n, d.h, d.w, d.ha, d.wa, d.c = z.n, z.h, z.w, z.ha, z.wa, c
     d.z, d.y = z.view(z_coff), y.view(y_coff)
