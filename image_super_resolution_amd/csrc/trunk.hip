@@ -38,15 +38,28 @@ size_t trunk_state_words(int n, int ha, int wa) {
 // err bits: 1 grid, 2 view geometry, 4 kind/cout, 8 cin/bias, 16 unsupported epilogue form,
 // 32 residual form, 64 a 16-channel plane of 2 GiB or more (one buffer resource spans one plane),
 // 128 too many layers.
+// Growth pairs (run_tile's PH forms): layers L and L + 1 are marked 1 and 2 in rec.deps bits 12-15
+// when both are kind 0 with the growth epilogue form, read the same planes of the same buffer,
+// L + 1 reads 32 channels more, and those 32 are exactly what L writes (first_new(L + 1) ==
+// cin(L) / 16); greedily from the left, where the order rule of trunk_pairs.h allows pairs for a
+// `grid`-workgroup launch and `pair_mode` (TRUNK_PAIRS_*) asks for them.  Geometry word r0 = the
+// number of paired layers.
 __global__ __launch_bounds__(1024) void trunk_prep_kernel(const isr_conv_desc* layers, const int32_t* kinds, int nl,
                                                           int n, int ha, int wa, unsigned* state, int th,
-                                                          int h16) {
+                                                          int h16, int grid, int pair_mode) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ unsigned char pairable[1024];  // layer L can pair with L + 1
+    __shared__ unsigned npaired;
     unsigned* err = reinterpret_cast<unsigned*>(smem);
     const int L = threadIdx.x;
     const int nbx = wa / tk::TW, nby = ha / th, ntiles = n * nbx * nby;
     const size_t ro = trunk_rec_off(ntiles);
-    if (L == 0) *err = 0;
+    const bool pairs_ok = pair_mode != TRUNK_PAIRS_OFF && pairs_allowed(ntiles, nbx, nby, n, grid);
+    if (L == 0) {
+        *err = 0;
+        npaired = 0;
+    }
+    pairable[L] = 0;
     __syncthreads();
     const isr_conv_desc& g0 = layers[0];
     if (L < nl) {
@@ -129,6 +142,29 @@ __global__ __launch_bounds__(1024) void trunk_prep_kernel(const isr_conv_desc* l
 #pragma unroll
         for (int i = 0; i < 16; ++i) dst[i] = src[i];
         if (e) atomicOr(err, e);
+        if (pairs_ok && !e && form == EPI_GROWTH && L + 1 < nl && kinds[L + 1] == 0) {
+            const isr_conv_desc& q = layers[L + 1];
+            const bool q_growth = !q.r1.data && !q.r2.data && q.s2 == 1.f && q.slope > 0.f && q.slope < 1.f;
+            const bool shared = q.x.data == d.x.data && q.x.coff == d.x.coff && q.cin == d.cin + 32;
+            const bool feeds = d.y.data == d.x.data && d.y.coff == d.x.coff + d.cin;
+            const bool wanted = pair_mode >= TRUNK_PAIRS_ALL || d.cin / 16 >= 8;
+            pairable[L] = q_growth && shared && feeds && wanted && q.cout == 32 && q.f16 == h16;
+        }
+    }
+    __syncthreads();
+    if (L < nl) {
+        // greedy from the left: inside a run of pairable layers every second one starts a pair
+        auto first_of_pair = [&](int i) {
+            if (i < 0 || !pairable[i]) return false;
+            int s = i;
+            while (s > 0 && pairable[s - 1]) --s;
+            return ((i - s) & 1) == 0;
+        };
+        const unsigned pb = first_of_pair(L) ? 1u : (first_of_pair(L - 1) ? 2u : 0u);
+        if (pb) {
+            state[ro + (size_t)L * 16 + 12] |= pb << 12;  // rec.deps (word 12), written by this thread above
+            atomicAdd(&npaired, 1u);
+        }
     }
     __syncthreads();
     if (L == 0) {
@@ -136,16 +172,16 @@ __global__ __launch_bounds__(1024) void trunk_prep_kernel(const isr_conv_desc* l
         const unsigned e = *err | (plane >= 0x7fffffffull ? 64u : 0u) | (nl > 1024 ? 128u : 0u);
         uint32_t* geo = state + ro - 16;
         const int32_t gv[16] = {n, g0.h, g0.w, ha, wa, g0.x.hp, g0.x.wp, g0.x.cs / 16, g0.x.pad, nbx, nby, ntiles,
-                                (int32_t)e, 0, 0, 0};
+                                (int32_t)e, (int32_t)npaired, 0, 0};
 #pragma unroll
         for (int i = 0; i < 16; ++i) geo[i] = (uint32_t)gv[i];
         state[0] = state[0] + 1u;  // this launch's generation (a vector store by one lane)
     }
 }
 
-int trunk_prep_launch(const isr_chain_desc* cd, int th, hipStream_t s) {
+int trunk_prep_launch(const isr_chain_desc* cd, int th, int grid, int pair_mode, hipStream_t s) {
     hipLaunchKernelGGL(trunk_prep_kernel, dim3(1), dim3(1024), 16, s, cd->layers, cd->kinds, cd->nl, cd->n, cd->ha,
-                       cd->wa, cd->state, th, cd->f16 ? 1 : 0);
+                       cd->wa, cd->state, th, cd->f16 ? 1 : 0, grid, pair_mode);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -244,6 +280,11 @@ struct Src {
     const float* b;  // bias
     int wpc;         // weight pieces per chunk (9 / 18)
     uint32_t xbytes, wbytes;  // extents of one activation plane and of the packed weights
+    // phase 1 of a growth pair (else nullptr): the second layer's record, for its 32-cout pack (two
+    // chunks longer than `w`) and its bias.  The chunk's 18 LDS pieces are the 64-cout image [tap][f]:
+    // piece 2 j = tap j of `w`, piece 2 j + 1 = tap j of the second pack, both at chunk * 9 + j of
+    // their own packs
+    const_rec* pb;
 };
 
 struct TrunkCtx {
@@ -268,6 +309,11 @@ __device__ __forceinline__ Src src_of(const TrunkCtx& c, const_rec& rec, int t) 
     s.wpc = rec_kind(rec) == 1 ? tk::WPF : tk::WPG;  // 64 / 32 couts (kinds 0 and 2: 32)
     s.xbytes = c.pstride;
     s.wbytes = (uint32_t)(rec_nch(rec) * s.wpc * 1024);
+    s.pb = nullptr;
+    if (rec_pair(rec) == 1) {
+        s.pb = &rec + 1;
+        s.wpc = tk::WPF;  // LDS pieces per chunk; wbytes stays the extent of the 32-cout pack
+    }
     return s;
 }
 
@@ -293,21 +339,39 @@ __device__ __forceinline__ uint32_t stage_pieces(const uint32_t* hoff, uint32_t 
             }
         }
     }
-    const auto rw = rsrc_n(s.w, s.wbytes);
-    const uint32_t wo = (uint32_t)(chunk * s.wpc * 1024);
+    // a pair's piece j = wave + WM k has the wave's parity (WM is even): one pack per wave
+    static_assert(TK::WM % 2 == 0, "pair staging: a wave's pieces all come from one pack");
+    const bool pair = s.pb != nullptr, second = pair && (wave & 1);
+    const char* wsrc = s.w;
+    uint32_t wext = s.wbytes;
+    if (second) {
+        wsrc = (const char*)(uintptr_t)s.pb->w;
+        wext += 2 * tk::WPG * 1024;  // the second layer reads two chunks more
+    }
+    const auto rw = rsrc_n(wsrc, wext);
+    const uint32_t wo = (uint32_t)(chunk * (pair ? tk::WPG : s.wpc) * 1024);
     char* wd = dst + TK::HP * 1024;
 #pragma unroll
     for (int k = 0; k < TK::WPW; ++k) {
         const int j = wave + TK::WM * k;
         if (j < s.wpc && !(abl & 8)) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(wd + j * 1024), 16, lane * 16, wo + j * 1024, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(wd + j * 1024), 16, lane * 16,
+                                                     wo + (pair ? j >> 1 : j) * 1024, 0, 0);
             ++n;
         }
     }
     if (with_bias && wave == 0) {
-        if (lane < (s.wpc == tk::WPG ? 32 : 64))  // cout floats only
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(s.b, s.wpc == tk::WPG ? 128u : 256u),
-                                                     ISR_LDS_PTR(smem + TK::BIAS_OFF + bslot * 256), 4, lane * 4, 0, 0, 0);
+        char* bd = smem + TK::BIAS_OFF + bslot * 256;
+        if (pair) {  // couts [0, 32) = the first layer's bias, [32, 64) = the second's
+            if (lane < 32) {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(s.b, 128u), ISR_LDS_PTR(bd), 4, lane * 4, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n((const float*)(uintptr_t)s.pb->b, 128u), ISR_LDS_PTR(bd + 128), 4, lane * 4, 0, 0, 0);
+            }
+            ++n;
+        } else if (lane < (s.wpc == tk::WPG ? 32 : 64)) {  // cout floats only
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_n(s.b, s.wpc == tk::WPG ? 128u : 256u), ISR_LDS_PTR(bd), 4,
+                                                     lane * 4, 0, 0, 0);
+        }
         ++n;
     }
     return n;
@@ -319,7 +383,7 @@ __device__ __forceinline__ uint32_t stage_chunk(const TrunkCtx& c, const Src& s,
     // tuning-build check of the ring protocol: the chunk lies inside the layer (chunk < nch: its
     // weights inside the packed table) and the slot inside the ring.  A violation gives the launch
     // up (the host raises) and issues nothing, instead of a DMA to a wrong place.
-    if (chunk < 0 || (uint32_t)(chunk * s.wpc * 1024) >= s.wbytes || slot < 0 || slot >= TK::NST ||
+    if (chunk < 0 || (uint32_t)(chunk * (s.pb ? tk::WPG : s.wpc) * 1024) >= s.wbytes || slot < 0 || slot >= TK::NST ||
         bslot < 0 || bslot > 3) {
         if (threadIdx.x == 0) {
             __hip_atomic_store(c.state + 1, c.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -387,16 +451,17 @@ __device__ __forceinline__ void force_publish(const TrunkCtx& c, Stream& st) {
 }
 
 // The tile after (L, t) in workgroup b's stream of a G-workgroup grid: the next tile of the same
-// layer, else the workgroup's first tile of the next layer; false at the end of the stream.
-__device__ __forceinline__ bool next_item(int L, int t, int b, int G, int ntiles, int nl, int& nL, int& nt) {
+// layer, else the workgroup's first tile of the next layer; false at the end of the stream.  A growth
+// pair is one item of `step` = 2 layers: the same pair at t + G, else layer L + 2.
+__device__ __forceinline__ bool next_item(int L, int step, int t, int b, int G, int ntiles, int nl, int& nL, int& nt) {
     nL = L;
     nt = t;
     if (t + G < ntiles) {
         nt = t + G;
         return true;
     }
-    if (L + 1 < nl) {
-        nL = L + 1;
+    if (L + step < nl) {
+        nL = L + step;
         nt = b;
         return true;
     }
@@ -442,12 +507,26 @@ enum : int {
 // Both forms keep the same stream state and hand-off protocol, so their tiles follow each other in
 // one stream, and the same MFMA, fold and epilogue order: the outputs are bit-identical.  The prep
 // kernel guarantees nch >= 4.
-template <int NF, bool MASKED = false, bool H = false>
+//
+// Growth pairs (PH; the prep kernel marks them): layers L and L + 1 of an RDB read the same chunks
+// 0..nch(L)-1, and L + 1 then two more, the output of L.  One pair item per tile stages the shared
+// chunks once:
+//  * PH 1 (NF = 2, L = the first layer): the shared chunks with the 64-cout chunk bodies, fragment 0
+//    = layer L, fragment 1 = layer L + 1 (weight pieces interleaved from the two 32-cout packs, the
+//    two biases in one bias slot, no fold); its last chunk stages nothing; the growth epilogue on
+//    fragment 0 alone, pending publish L + 1; fragment 1's accumulators leave in `pacc`;
+//  * PH 2 (NF = 1, L = the second layer): its last two chunks on `pacc`.  The first is always staged
+//    at its own top (drain the stores, publish, wait for the neighbourhood's layer L - 1, stage); the
+//    second stages the next item's chunk 0 as any last chunk does.  Growth epilogue, publish L + 1.
+// Each accumulator receives the MFMAs of its per-layer tile in the same order (chunk ascending, then
+// dx, dy, row, the same for NF 1 and 2), so the bits are those of the unpaired stream.
+template <int NF, bool MASKED = false, bool H = false, int PH = 0>
 __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_rec* recs, int L, int t,
-                                         int nxL, int nxt, bool nx_exists) {
+                                         int nxL, int nxt, bool nx_exists, f32x16* pacc = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int R = TK::R, NST = TK::NST, CT = 32 * NF, TN = 3, NA = R + 2;
     constexpr bool ROLES = !MASKED;
+    static_assert(PH == 0 || (!MASKED && NF == (PH == 1 ? 2 : 1)), "pair phases: 64-cout bodies, then 32-cout");
     // The 64-cout layers (128 accumulator + 96 fragment VGPRs) keep one chunk body per fold position
     // plus one loop body (CR_LOOP: run-time slot, run-time boundary / last test): with alternative
     // chunk bodies in the arms of a branch, or the steady run split into several loops, hipcc moves
@@ -455,6 +534,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     // (DESIGN.md section 5).  The 32-cout layers take the full form: compile-time slots, split run.
     constexpr bool FULL = ROLES && NF == 1;
     constexpr int WPC = NF == 2 ? tk::WPF : tk::WPG;  // weight pieces per chunk of a forward layer
+    constexpr int WSTEP = PH == 1 ? tk::WPG : WPC;    // pieces per chunk in one weight pack
     const_rec& rec = recs[L];
     const int wave = wave_id(), lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
     const int bx = t % c.nbx, tmp = t / c.nbx, by = tmp % c.nby, img = tmp / c.nby;
@@ -462,8 +542,8 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     const int nch = rec_nch(rec);
     const int first_new = rec_first_new(rec);  // NEED_NONE on layer 0
     const unsigned need = c.gen * 1024u + (unsigned)L;  // the neighbourhood is done with layer L-1
-    const bool fold = NF == 2 && rec_fold(rec);
-    const bool has_r2 = NF == 2 && rec.r2 != 0;
+    const bool fold = NF == 2 && PH == 0 && rec_fold(rec);
+    const bool has_r2 = NF == 2 && PH == 0 && rec.r2 != 0;
     constexpr bool masked = NF == 1 && MASKED;  // kind 2 (gather conv): LeakyReLU' mask from rec.r2
     const Src me = src_of(c, rec, t);
     // general form: the next item's source up front (the roles compute it in the last chunk)
@@ -480,9 +560,19 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     }
     // roles: the plane of the next chunk to stage (advanced by pstride per chunk) and that chunk's
     // offset in the weight table
-    const char* xn = me.x;
-    uint32_t wo = 0;
-    bool dep_ok = first_new == tk::NEED_NONE || st.dep_next;
+    const int ch0 = PH == 2 ? nch - 2 : 0;  // the tile's first chunk
+    // the pack this wave stages from (pair phase 1: odd waves stage the second layer's pieces)
+    const char* w_own = me.w;
+    uint32_t wext_own = me.wbytes;
+    if constexpr (PH == 1) {
+        if (wave & 1) {
+            w_own = (const char*)(uintptr_t)recs[L + 1].w;
+            wext_own += 2 * tk::WPG * 1024;
+        }
+    }
+    const char* xn = me.x + (size_t)ch0 * c.pstride;
+    uint32_t wo = (uint32_t)(ch0 * WSTEP * 1024);
+    bool dep_ok = PH != 2 && (first_new == tk::NEED_NONE || st.dep_next);
     st.dep_next = false;
     const int bslot = st.tseq & 3;
     const int first_item = st.item;  // this tile's chunk 0
@@ -522,23 +612,29 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
             }
         }
         if (!(c.abl & 8)) {
-            const auto rw = rsrc_n(me.w, me.wbytes);
+            // pair phase 1: LDS piece j = tap j / 2 of the first (j even) or second (j odd) layer's
+            // pack; j has the wave's parity, so a wave reads one pack
+            const auto rw = rsrc_n(w_own, wext_own);
 #pragma unroll
             for (int k = 0; k < (WPC + TK::WM - 1) / TK::WM; ++k) {
                 const int j = wave + TK::WM * k;
                 if (TK::WM * k + TK::WM <= WPC || j < WPC) {
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(dst + (TK::HP + j) * 1024), 16, lane * 16,
-                                                             wo + j * 1024, 0, 0);
+                                                             wo + (PH == 1 ? j >> 1 : j) * 1024, 0, 0);
                     ++n;
                 }
             }
         }
         xn += c.pstride;
-        wo += WPC * 1024;
+        wo += WSTEP * 1024;
         return n;
     };
 
     f32x16 acc[R][NF];
+    if constexpr (PH == 2) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r][0] = pacc[r];  // phase 1 left them: bias and the shared chunks
+    }
 
     // one K-chunk; FC = the chunk index (0..3) when the residual fold adds its MFMAs to it, else -1
     // (peeled so that the fold's target accumulator is compile-time: a run-time choice made hipcc
@@ -557,17 +653,18 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                 if (st.staged < st.item) {
                     // not staged (the previous tile's outputs lie in this tile's neighbourhood): drain,
                     // publish, wait, stage
+                    // (pair phase 2 always comes here: phase 1 just wrote this chunk and staged nothing)
                     force_publish(c, st);
-                    if (first_new == 0 && !dep_ok) {
+                    if ((PH == 2 || first_new == 0) && !dep_ok) {
                         wait_deps(t, need);
                         dep_ok = true;
                     }
-                    st.issued += stage_chunk(c, me, 0, slot, true, bslot);
+                    st.issued += stage_chunk(c, me, ch, slot, PH != 2, bslot);
                     st.staged = st.item;
                     st.m0 = st.issued;
                 }
-                xn += c.pstride;  // chunk 0 is staged: the next chunk to stage is chunk 1
-                wo += WPC * 1024;
+                xn += c.pstride;  // the first chunk is staged: the next chunk to stage is the second
+                wo += WSTEP * 1024;
                 wait_vm_coarse(st.issued - st.m0);
             } else if constexpr (ROLE != CR_GENERAL) {
 #ifdef ISR_TUNING
@@ -606,7 +703,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                 st.pend_t = -1;
             }
             }
-            if (ROLE == CR_FIRST || (ROLE == CR_GENERAL && ch == 0)) {
+            if (PH != 2 && (ROLE == CR_FIRST || (ROLE == CR_GENERAL && ch == 0))) {
                 trunk_stamp(L, t, c.ntiles, 1);
                 // bias → accumulators (register g of lane l: cout (g&3) + 8(g>>2) + 4hh of fragment f)
                 const float* bs = reinterpret_cast<const float*>(smem + TK::BIAS_OFF + bslot * 256);
@@ -655,8 +752,9 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
             // ---- refill: stage the stream one item ahead (this tile's next chunk, else the next
             // tile's chunk 0), in one block after step 0's reads ----
             const bool last = ROLE == CR_LAST || (ROLE == CR_LOOP && ch == nch - 1);
-            if constexpr (ROLE == CR_LAST || ROLE == CR_LOOP) {
+            if constexpr ((ROLE == CR_LAST || ROLE == CR_LOOP) && PH != 1) {
                 // the next item's chunk 0 (with its bias), unless it needs this tile's own outputs
+                // (pair phase 1: the next item is its own phase 2, which does)
                 if (last && nx_exists && ring_ok) {
                     const_rec& nrec = recs[nxL];
                     bool go = true;
@@ -756,14 +854,18 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     };
     if constexpr (ROLES) {
         // a chunk in the slot the stream has reached (a tile starts on either slot: counts may be odd)
-        int ch = 0;
+        int ch = ch0;
         auto in_slot = [&](auto fc_tag, auto role_tag) {
             if constexpr (!FULL) do_chunk(ch, fc_tag, TIC<-1>{}, role_tag);
             else if (st.item & 1) do_chunk(ch, fc_tag, TIC<1>{}, role_tag);
             else do_chunk(ch, fc_tag, TIC<0>{}, role_tag);
             ++ch;
         };
-        if constexpr (NF == 2) {
+        if constexpr (PH == 2) {  // straight-line: the two chunks phase 1 wrote
+            in_slot(TIC<-1>{}, TIC<CR_FIRST>{});
+            in_slot(TIC<-1>{}, TIC<CR_LAST>{});
+        }
+        if constexpr (NF == 2 && PH == 0) {
             if (fold) {  // the residual fold's chunks 0-3, peeled
                 in_slot(TIC<0>{}, TIC<CR_FIRST>{});
                 in_slot(TIC<1>{}, TIC<CR_SECOND>{});
@@ -771,10 +873,12 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                 in_slot(TIC<3>{}, TIC<CR_LOOP>{});  // the last chunk of a 64-channel input
             }
         }
+        if constexpr (PH != 2)
         if (ch == 0) {
             in_slot(TIC<-1>{}, TIC<CR_FIRST>{});
             in_slot(TIC<-1>{}, TIC<CR_SECOND>{});
         }
+        if constexpr (PH != 2)
         if (ch < nch) {
             // steady chunks [ch, nch - 1), split at the chunk `wb` whose refill stages chunk first_new
             const int wb = first_new - 1;
@@ -824,7 +928,8 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     auto epilogue = [&](auto form_tag, auto full_tag) {
         constexpr int EF = decltype(form_tag)::value;
         constexpr bool GEN = EF == EPI_GENERAL, FT = decltype(full_tag)::value != 0;
-        static_assert(GEN || (EF == EPI_GROWTH ? NF == 1 && !MASKED : NF == 2), "form and layer kind");
+        static_assert(GEN || (EF == EPI_GROWTH ? (NF == 1 || PH == 1) && !MASKED : NF == 2 && PH == 0),
+                      "form and layer kind");
         const bool use_r2 = GEN ? (has_r2 || masked) : EF == EPI_FINAL_R2;
         // the body's marker in the assembly (tools/trunk_isa_mix.py) and the LeakyReLU's 0.0f as a
         // value of this body alone: compared with the literal, the 64 compares of a growth tile were
@@ -866,7 +971,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
             const bool valid = yy < c.h && xx < c.w;
             const uint32_t pix = (uint32_t)((yy + c.pad) * c.wp + xx + c.pad);
 #pragma unroll
-            for (int f = 0; f < NF; ++f) {
+            for (int f = 0; f < (PH == 1 ? 1 : NF); ++f) {  // pair phase 1: fragment 0 is the layer
                 float v[16];
                 if constexpr (GEN) {
 #pragma unroll
@@ -948,7 +1053,9 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
         else epilogue(form_tag, TIC<0>{});
     };
     const int form = ROLES ? rec_form(rec) : (int)EPI_GENERAL;
-    if constexpr (ROLES && NF == 1) {
+    if constexpr (PH != 0) {
+        epilogue_of(TIC<EPI_GROWTH>{});  // the prep kernel pairs layers of the growth form only
+    } else if constexpr (ROLES && NF == 1) {
         if (form == EPI_GROWTH) epilogue_of(TIC<EPI_GROWTH>{});
         else epilogue(TIC<EPI_GENERAL>{}, TIC<0>{});
     } else if constexpr (ROLES) {
@@ -963,7 +1070,13 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     st.pend_t = t;
     st.pend_v = c.gen * 1024u + (unsigned)(L + 1);
     st.pend_mark = st.issued;
-    ++st.tseq;
+    if constexpr (PH == 1) {
+        // one bias slot per pair item: phase 2 ends the tile
+#pragma unroll
+        for (int r = 0; r < R; ++r) pacc[r] = acc[r][1];
+    } else {
+        ++st.tseq;
+    }
 }
 
 template <bool H>
@@ -1011,13 +1124,21 @@ __global__ __launch_bounds__(TK::NT, TK::WPS) void trunk_kernel(TrunkArgs a) {
     if (b < c.ntiles) {
         st.issued += stage_chunk(c, src_of(c, recs[0], b), 0, 0, true, 0);  // layer 0 reads the trunk input only
         st.m0 = st.issued;
-        for (int L = 0; L < a.nl; ++L) {
+        for (int L = 0, step; L < a.nl; L += step) {
             const_rec& rec = recs[L];
+            // a growth pair (layers L, L + 1) is one item per tile, pair-major: both phases of a tile
+            // before the workgroup's next tile
+            const bool pair = rec_pair(rec) == 1 && L + 1 < a.nl;
+            step = pair ? 2 : 1;
             for (int t = b; t < c.ntiles; t += G) {
                 int nxL, nxt;
-                const bool nx_exists = next_item(L, t, b, G, c.ntiles, a.nl, nxL, nxt);
+                const bool nx_exists = next_item(L, step, t, b, G, c.ntiles, a.nl, nxL, nxt);
                 const int kind = rec_kind(rec);
-                if (kind == 0) run_tile<1, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
+                if (pair) {
+                    f32x16 pacc[TK::R];
+                    run_tile<2, false, H, 1>(c, st, recs, L, t, nxL, nxt, nx_exists, pacc);
+                    run_tile<1, false, H, 2>(c, st, recs, L + 1, t, nxL, nxt, nx_exists, pacc);
+                } else if (kind == 0) run_tile<1, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
                 else if (kind == 2) run_tile<1, true, H>(c, st, recs, L, t, nxL, nxt, nx_exists);  // the backward chain's gathers
                 else run_tile<2, false, H>(c, st, recs, L, t, nxL, nxt, nx_exists);
             }
@@ -1060,7 +1181,10 @@ static int trunk_launch_k(const isr_chain_desc* cd, hipStream_t s) {
     const long long slots = (long long)per_cu * cached_cus;
     const int grid = (int)(ntiles < slots ? ntiles : slots);
     const int rec_off = (int)trunk_rec_off((int)ntiles);
-    trunk_prep_launch(cd, TK::TH, s);
+    // growth pairs: ISR_TRUNK_PAIRS = 0 none, 1 only pairs sharing 8 chunks or more, 2 all (the A/B
+    // switch of DESIGN.md section 5, Growth pairs), read once
+    static const int pair_mode = getenv("ISR_TRUNK_PAIRS") ? atoi(getenv("ISR_TRUNK_PAIRS")) : TRUNK_PAIRS_ALL;
+    trunk_prep_launch(cd, TK::TH, grid, pair_mode < 0 ? 0 : (pair_mode > 2 ? 2 : pair_mode), s);
     TrunkArgs a;
     a.state = cd->state;
     a.rec_off = rec_off;

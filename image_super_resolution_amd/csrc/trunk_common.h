@@ -2,6 +2,7 @@
 // poll, buffer resources, the LDS halo image, counted vmcnt waits.
 #pragma once
 #include "isr_common.h"
+#include "trunk_pairs.h"
 
 namespace isr {
 
@@ -20,10 +21,11 @@ struct TrunkRec {
     uint64_t x, y, w, b, r2;   // buffer bases, packed weights, fp32 bias, r2 base (or 0)
     uint32_t planes;           // xp | yp << 16: first 16-channel plane of x / y (coff / 16)
     uint32_t shape;            // r2p | nch << 16 | kind << 24 (nch = cin / 16; kind 0 growth, 1 final)
-    uint32_t deps;             // first_new | fold << 8 | form << 9 | idv << 16 (first chunk the
-                               // previous layer wrote, NEED_NONE on layer 0; fold: r1 == x[0:cout]
-                               // added as x/s1 by MFMA; form: the tile epilogue's form, EPI_*, 3
-                               // bits; idv: storage-type bits of 1/s1)
+    uint32_t deps;             // first_new | fold << 8 | form << 9 | pair << 12 | idv << 16 (first
+                               // chunk the previous layer wrote, NEED_NONE on layer 0; fold: r1 ==
+                               // x[0:cout] added as x/s1 by MFMA; form: the tile epilogue's form,
+                               // EPI_*, 3 bits; pair: 1 = first, 2 = second layer of a growth
+                               // pair, 4 bits; idv: storage-type bits of 1/s1)
     float slope, s1, s2;
 };
 static_assert(sizeof(TrunkRec) == 64, "record size");
@@ -60,6 +62,7 @@ __device__ __forceinline__ int rec_kind(const_rec_t& r) { return (int)(r.shape >
 __device__ __forceinline__ int rec_first_new(const_rec_t& r) { return (int)(r.deps & 255); }
 __device__ __forceinline__ bool rec_fold(const_rec_t& r) { return ((r.deps >> 8) & 1) != 0; }
 __device__ __forceinline__ int rec_form(const_rec_t& r) { return (int)((r.deps >> 9) & 7); }
+__device__ __forceinline__ int rec_pair(const_rec_t& r) { return (int)((r.deps >> 12) & 15); }
 __device__ __forceinline__ uint32_t rec_idv(const_rec_t& r) { return r.deps >> 16; }
 
 __device__ __forceinline__ void raw_barrier() {
@@ -175,6 +178,7 @@ __device__ __forceinline__ bf16x8 fold_a_bits(uint32_t idv, int h16) {
     return __builtin_bit_cast(bf16x8, r);
 }
 
-int trunk_prep_launch(const isr_chain_desc* cd, int th, hipStream_t s);
+// grid = workgroups of the trunk launch, pair_mode = TRUNK_PAIRS_* (trunk_pairs.h)
+int trunk_prep_launch(const isr_chain_desc* cd, int th, int grid, int pair_mode, hipStream_t s);
 
 }  // namespace isr
