@@ -122,6 +122,14 @@ class IsrIsoNoiseDesc(ctypes.Structure):
                 ("lum_noise", c_void_p), ("hue_noise", c_void_p), ("apply", c_void_p)]
 
 
+class IsrResampleDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("in_h", c_int32), ("in_w", c_int32), ("out_h", c_int32), ("out_w", c_int32),
+                ("nf", c_int32), ("ksize_x", c_int32), ("ksize_y", c_int32), ("src", c_void_p),
+                ("bounds_x", c_void_p), ("coeffs_x", c_void_p), ("bounds_y", c_void_p), ("coeffs_y", c_void_p),
+                ("filter_id", c_void_p), ("dst_u8", c_void_p), ("lr_f32", c_void_p), ("hr_f32", c_void_p),
+                ("hr_norm", c_int32), ("mean", c_float * 3), ("std", c_float * 3)]
+
+
 HLS_PARTIAL_BLOCKS = 32  # ISR_HLS_PARTIAL_BLOCKS
 MT_TENSOR_BYTES = 40 # isr_mt_tensor: 4 pointers + int64
 MT_CHUNK_BYTES = 16   # isr_mt_chunk: int32 t, int32 len, int64 start
@@ -196,6 +204,9 @@ SIGNATURES = {
     "isr_jpeg_roundtrip": (c_int32, [POINTER(IsrJpegDesc), c_void_p, c_size_t, c_void_p]),
     "isr_hls_l_moments": (c_int32, [POINTER(IsrHlsMomentsDesc), c_void_p]),
     "isr_iso_noise": (c_int32, [POINTER(IsrIsoNoiseDesc), c_void_p]),
+    "isr_resample_ksize": (c_int32, [c_int32, c_int32, c_int32]),
+    "isr_resample_tables": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "isr_resample_u8": (c_int32, [POINTER(IsrResampleDesc), c_void_p]),
     "isr_last_error": (ctypes.c_char_p, []),
     "isr_version": (c_int32, []),
 }

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "isr_common.h"
+#include "resample_tables.h"
 
 namespace isr {
 int conv3x3_fwd_dispatch(const isr_conv_desc* d, hipStream_t s);
@@ -57,6 +58,7 @@ size_t jpeg_roundtrip_workspace_bytes(const isr_jpeg_desc* d);
 int jpeg_roundtrip_dispatch(const isr_jpeg_desc* d, void* ws, size_t ws_bytes, hipStream_t s);
 int hls_l_moments_dispatch(const isr_hls_moments_desc* d, hipStream_t s);
 int iso_noise_dispatch(const isr_iso_noise_desc* d, hipStream_t s);
+int resample_u8_dispatch(const isr_resample_desc* d, hipStream_t s);
 }  // namespace isr
 
 static thread_local char g_err[512] = "";
@@ -753,6 +755,67 @@ int isr_iso_noise(const isr_iso_noise_desc* d, isr_stream_t s) {
     if ((hw + 255) / 256 >= (1ll << 31))
         return fail(ISR_ERR_UNSUPPORTED, "iso_noise: %dx%d needs more than 2^31 - 1 workgroups per image", d->h, d->w);
     return launched(isr::iso_noise_dispatch(d, (hipStream_t)s), "iso_noise");
+}
+
+static int resample_axis_check(const char* what, int filter, int in_size, int out_size) {
+    switch (isr::resample_check(filter, in_size, out_size)) {
+        case 0: return ISR_OK;
+        case 1: return fail(ISR_ERR_UNSUPPORTED, "%s: unknown filter %d (ISR_RESAMPLE_NEAREST..LANCZOS = 0..5)", what, filter);
+        case 2: return fail(ISR_ERR_UNSUPPORTED, "%s: sizes %d -> %d outside [1, %d]", what, in_size, out_size,
+                            isr::RESAMPLE_MAX_SIZE);
+        default: return fail(ISR_ERR_UNSUPPORTED, "%s: ratio %d -> %d outside [1/%d, %d]", what, in_size, out_size,
+                             isr::RESAMPLE_MAX_RATIO, isr::RESAMPLE_MAX_RATIO);
+    }
+}
+
+int isr_resample_ksize(int filter, int in_size, int out_size) {
+    if (resample_axis_check("resample_ksize", filter, in_size, out_size) != ISR_OK) return 0;
+    g_err[0] = 0;
+    return isr::resample_ksize(filter, in_size, out_size);
+}
+
+int isr_resample_tables(int filter, int in_size, int out_size, int32_t* bounds, int32_t* coeffs) {
+    if (!bounds || !coeffs) return fail(ISR_ERR_BAD_DESC, "resample_tables: null bounds / coeffs");
+    const int rc = resample_axis_check("resample_tables", filter, in_size, out_size);
+    if (rc != ISR_OK) return rc;
+    isr::resample_tables(filter, in_size, out_size, bounds, coeffs);
+    g_err[0] = 0;
+    return ISR_OK;
+}
+
+int isr_resample_u8(const isr_resample_desc* d, isr_stream_t s) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "resample_u8: null descriptor");
+    if (!d->src || !d->bounds_x || !d->coeffs_x || !d->bounds_y || !d->coeffs_y)
+        return fail(ISR_ERR_BAD_DESC, "resample_u8: null src / tables");
+    if (!d->dst_u8 && !d->lr_f32 && !d->hr_f32) return fail(ISR_ERR_BAD_DESC, "resample_u8: no output requested");
+    if (d->n < 1 || d->n > 65535 || d->nf < 1)
+        return fail(ISR_ERR_BAD_DESC, "resample_u8: bad batch n=%d nf=%d (n in [1, 65535], nf >= 1)", d->n, d->nf);
+    // filter 1 stands in for the size and ratio rules, which are the same for every filter
+    int rc = resample_axis_check("resample_u8 (height)", 1, d->in_h, d->out_h);
+    if (rc != ISR_OK) return rc;
+    rc = resample_axis_check("resample_u8 (width)", 1, d->in_w, d->out_w);
+    if (rc != ISR_OK) return rc;
+    if (d->ksize_x < 1 || d->ksize_x > ISR_RESAMPLE_MAX_KSIZE || d->ksize_y < 1 || d->ksize_y > ISR_RESAMPLE_MAX_KSIZE)
+        return fail(ISR_ERR_UNSUPPORTED, "resample_u8: ksize %d / %d outside [1, %d]", d->ksize_x, d->ksize_y,
+                    ISR_RESAMPLE_MAX_KSIZE);
+    if (d->hr_f32 && (d->in_h % d->out_h || d->in_w % d->out_w))
+        return fail(ISR_ERR_UNSUPPORTED, "resample_u8: hr_f32 needs an integer ratio on both axes, got %dx%d -> %dx%d",
+                    d->in_h, d->in_w, d->out_h, d->out_w);
+    if ((long long)d->n * 3 * d->in_h * d->in_w >= (1ll << 31) || (long long)d->n * 3 * d->out_h * d->out_w >= (1ll << 31))
+        return fail(ISR_ERR_UNSUPPORTED, "resample_u8: n*3*h*w does not fit 31 bits (n=%d, %dx%d -> %dx%d)", d->n,
+                    d->in_h, d->in_w, d->out_h, d->out_w);
+    if (d->dst_u8 == d->src) return fail(ISR_ERR_BAD_DESC, "resample_u8: dst_u8 must not be src");
+    if (((uintptr_t)d->src | (uintptr_t)d->dst_u8 | (uintptr_t)d->bounds_x | (uintptr_t)d->coeffs_x |
+         (uintptr_t)d->bounds_y | (uintptr_t)d->coeffs_y | (uintptr_t)d->filter_id) % 4 ||
+        ((uintptr_t)d->lr_f32 | (uintptr_t)d->hr_f32) % 16)
+        return fail(ISR_ERR_BAD_DESC, "resample_u8: src, dst_u8, tables and filter_id must be 4-byte aligned, lr_f32 "
+                    "and hr_f32 16-byte aligned");
+    if (d->lr_f32 || (d->hr_f32 && d->hr_norm))
+        for (int c = 0; c < 3; ++c)
+            if (!(d->std[c] != 0.f)) return fail(ISR_ERR_BAD_DESC, "resample_u8: std[%d] is zero", c);
+    rc = isr::resample_u8_dispatch(d, (hipStream_t)s);
+    if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "resample_u8: more than 2^31 - 1 workgroups");
+    return launched(rc, "resample_u8");
 }
 
 }  // extern "C"

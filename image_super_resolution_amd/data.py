@@ -77,16 +77,35 @@ class GPUTransform:
     samples at src = scale*(d + 0.5) - 0.5 with weights 0 / 0.5 / 1, i.e. the exact float
     bilinear value rounded half up — reproduced here by rounding the float interpolation
     of the uint8 values (oracle.ref_cpu.cv2_resize_linear_u8 restates the fixed-point
-    arithmetic; tests/test_data_cpu.py)."""
+    arithmetic; tests/test_data_cpu.py).
 
-    def __init__(self, scale: int, hr_norm: bool = False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
+    `lr_filter` chooses the LR model.  "cv2" (the default) is the above, SR_dataset's.  A name of
+    degrade.RESAMPLE_FILTERS ("bicubic", ...) makes the LR with Pillow's antialiased Image.resize
+    instead, bit for bit (Random_low_rs, utils/datasets.py:23-32), hr and lr still in ONE launch
+    (isr_resample_u8).  "random" is image_reader's mix (:218-246): per image one of RANDOM_FILTERS
+    = (bicubic, bilinear, box, nearest), each with probability 0.25, drawn by exactly one
+    torch.randint(0, 4, (n,), generator=self.gen, device=...) per call (self.gen seeded with
+    `seed`) and never read back.  These are HIP kernels: on a CPU device they raise."""
+
+    LR_FILTERS = ("cv2", "nearest", "box", "bilinear", "hamming", "bicubic", "lanczos", "random")
+    RANDOM_FILTERS = ("bicubic", "bilinear", "box", "nearest")
+
+    def __init__(self, scale: int, hr_norm: bool = False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda",
+                 lr_filter: str = "cv2", seed: int = 0):
+        if lr_filter not in self.LR_FILTERS:
+            raise ValueError(f"GPUTransform: lr_filter {lr_filter!r} is not one of {', '.join(self.LR_FILTERS)}")
         self.scale, self.hr_norm = scale, hr_norm
+        self.lr_filter, self.seed, self.gen = lr_filter, seed, None
+        if lr_filter == "random" and torch.device(device).type == "cuda":
+            self.gen = torch.Generator(device=device).manual_seed(seed)
         self.mean = torch.tensor(mean, device=device).view(1, 3, 1, 1)
         self.std = torch.tensor(std, device=device).view(1, 3, 1, 1)
         self.mean_f, self.std_f = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self.device = device
 
     def __call__(self, crops_u8: torch.Tensor):
+        if self.lr_filter != "cv2":
+            return self._hip_resample(crops_u8)
         if torch.device(self.device).type == "cuda":
             return self._hip(crops_u8)
         # CPU device: the same formulas as torch ops (host-side tests; the GPU path is the kernel)
@@ -118,6 +137,29 @@ class GPUTransform:
                                     int(self.hr_norm), (ctypes.c_float * 3)(*self.mean_f),
                                     (ctypes.c_float * 3)(*self.std_f))
         _lib.check(_lib.load().isr_sr_transform(ctypes.byref(d), ops._stream()), "isr_sr_transform")
+        return hr, lr
+
+    def _hip_resample(self, crops_u8: torch.Tensor):
+        """One HIP launch (isr_resample_u8): Pillow's resize to LR, both Normalizes, the HR tensor."""
+        from . import degrade
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError(f"GPUTransform: lr_filter={self.lr_filter!r} is a HIP kernel (MI355X only); device "
+                               f"{self.device!r} has no such path (there is no host fallback)")
+        if crops_u8.dtype != torch.uint8 or crops_u8.dim() != 4 or crops_u8.shape[1] != 3:
+            raise ValueError(f"GPUTransform expects uint8 [n, 3, t, t] crops, got {crops_u8.dtype} "
+                             f"{tuple(crops_u8.shape)}")
+        n, _, t, tw = crops_u8.shape
+        if t != tw or t % self.scale:
+            raise ValueError(f"GPUTransform: square crops with side a multiple of {self.scale}, got {t}x{tw}")
+        x = crops_u8.to(self.device, non_blocking=True).contiguous()
+        if self.lr_filter == "random":
+            names = self.RANDOM_FILTERS
+            ids = torch.randint(0, 4, (n,), generator=self.gen, device=x.device).to(torch.int32)
+        else:
+            names, ids = (self.lr_filter,), None
+        filters = tuple(degrade.RESAMPLE_FILTERS.index(f) for f in names)
+        _, lr, hr = degrade.resample_launch(x, (t // self.scale, t // self.scale), filters, ids, want_lr=True,
+                                            want_hr=True, hr_norm=self.hr_norm, mean=self.mean_f, std=self.std_f)
         return hr, lr
 
 

@@ -4,12 +4,17 @@ albumentations ImageCompression and ISONoise), on uint8 [n, 3, h, w] RGB crops t
 the GPU.  Nothing here synchronises with the host: per-image qualities and apply flags are device
 tensors, and a quality of 0 / an apply flag of 0 copies the image through.
 
+`resample_u8` is Pillow's Image.resize (antialiased bicubic ... nearest) on such a batch, bit for
+bit: the LR models of the reference's Random_low_rs and image_reader (utils/datasets.py:23-32,
+:218-246).  Its coefficient tables are made on the host by libisr (`resample_tables`, plain C++).
+
 GPU-only, like the rest of the product path: a CPU tensor raises.
 """
 from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -110,3 +115,92 @@ def iso_noise(u8: torch.Tensor, color_shift, intensity, generator: torch.Generat
         lum = torch.poisson(lam.view(n, 1, 1).expand(n, h, w).contiguous(), generator=generator)
         hue = torch.randn((n, h, w), device=x.device, generator=generator) * (cs * 360.0 * it).view(n, 1, 1)
         return iso_noise_planes(x, lum, hue, apply)
+
+
+RESAMPLE_FILTERS = ("nearest", "box", "bilinear", "hamming", "bicubic", "lanczos")  # index = ISR_RESAMPLE_*
+
+
+def _filter_index(f) -> int:
+    if isinstance(f, str):
+        if f not in RESAMPLE_FILTERS:
+            raise ValueError(f"resample: unknown filter {f!r}; one of {', '.join(RESAMPLE_FILTERS)}")
+        return RESAMPLE_FILTERS.index(f)
+    if int(f) != f or not 0 <= int(f) < len(RESAMPLE_FILTERS):
+        raise ValueError(f"resample: filter id {f!r} not in 0..{len(RESAMPLE_FILTERS) - 1}")
+    return int(f)
+
+
+def resample_tables(filter, in_size: int, out_size: int):
+    """Pillow's coefficient table of one axis from libisr's host code (no GPU): numpy int32
+    bounds [out_size, 2] = (first source index, tap count) and coeffs [out_size, ksize] (22
+    fractional bits, rows zero-padded).  `filter`: a name of RESAMPLE_FILTERS or its index."""
+    f, lib = _filter_index(filter), _lib.load()
+    in_size, out_size = int(in_size), int(out_size)
+    ks = lib.isr_resample_ksize(f, in_size, out_size)
+    if ks <= 0:
+        raise _lib.IsrError("isr_resample_ksize refused: " + lib.isr_last_error().decode(errors="replace"))
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    coeffs = np.zeros((out_size, ks), dtype=np.int32)
+    _lib.check(lib.isr_resample_tables(f, in_size, out_size, bounds.ctypes.data, coeffs.ctypes.data),
+               "isr_resample_tables")
+    return bounds, coeffs
+
+
+_resample_cache: dict = {}
+
+
+def _device_tables(device: torch.device, in_size: int, out_size: int, filters: tuple):
+    """(bounds [nf, out, 2], coeffs [nf, out, ksize], ksize) on `device` for the filter variants
+    `filters` (indices), padded to their common ksize; cached per (device, in, out, filters)."""
+    key = (device.type, device.index, in_size, out_size, filters)
+    hit = _resample_cache.get(key)
+    if hit is None:
+        tabs = [resample_tables(f, in_size, out_size) for f in filters]
+        ks = max(c.shape[1] for _, c in tabs)
+        bounds = np.stack([b for b, _ in tabs])
+        coeffs = np.zeros((len(tabs), out_size, ks), dtype=np.int32)
+        for i, (_, c) in enumerate(tabs):
+            coeffs[i, :, :c.shape[1]] = c
+        hit = (torch.from_numpy(bounds).to(device), torch.from_numpy(coeffs).to(device), ks)
+        _resample_cache[key] = hit
+    return hit
+
+
+def resample_launch(x: torch.Tensor, size, filters: tuple, filter_id: torch.Tensor | None, *, want_u8: bool = False,
+                    want_lr: bool = False, want_hr: bool = False, hr_norm: bool = False, mean=(0.0, 0.0, 0.0),
+                    std=(1.0, 1.0, 1.0)):
+    """One isr_resample_u8 launch on a checked uint8 [n, 3, h, w] device batch: returns
+    (dst_u8, lr_f32, hr_f32), None for what was not asked for.  `filters`: the variants' filter
+    indices; `filter_id`: device int32 [n] picking a variant per image, or None for variant 0."""
+    n, _, h, w = x.shape
+    oh, ow = (int(v) for v in size)
+    with torch.cuda.device(x.device):
+        bx, cx, ksx = _device_tables(x.device, w, ow, filters)
+        by, cy, ksy = _device_tables(x.device, h, oh, filters)
+        dst = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=x.device) if want_u8 else None
+        lr = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=x.device) if want_lr else None
+        hr = torch.empty((n, 3, h, w), dtype=torch.float32, device=x.device) if want_hr else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        d = _lib.IsrResampleDesc(n, h, w, oh, ow, len(filters), ksx, ksy, x.data_ptr(), bx.data_ptr(), cx.data_ptr(),
+                                 by.data_ptr(), cy.data_ptr(), ptr(filter_id), ptr(dst), ptr(lr), ptr(hr),
+                                 int(hr_norm), (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std))
+        _lib.check(_lib.load().isr_resample_u8(ctypes.byref(d), _stream()), "isr_resample_u8")
+    return dst, lr, hr
+
+
+def resample_u8(u8: torch.Tensor, size, filter="bicubic") -> torch.Tensor:
+    """Pillow's Image.resize of every image to size = (h, w), bit for bit (two int32 passes with a
+    uint8 image between them; antialiased on a downscale).  `filter`: a name of RESAMPLE_FILTERS
+    for the whole batch, or an int tensor / sequence [n] of per-image indices into it (a device
+    tensor stays on the device; the kernel clamps ids to 0..5).  Each axis' ratio must lie in
+    [1/8, 8]."""
+    x = _checked(u8, "resample_u8")
+    n = x.shape[0]
+    if isinstance(filter, (str, int)):
+        return resample_launch(x, size, (_filter_index(filter),), None, want_u8=True)[0]
+    if isinstance(filter, torch.Tensor) and (filter.is_floating_point() or filter.dtype == torch.bool):
+        raise ValueError(f"resample_u8: filter ids must be an integer tensor, got {filter.dtype}")
+    ids = filter if isinstance(filter, torch.Tensor) else torch.tensor([int(f) for f in filter], dtype=torch.int32)
+    with torch.cuda.device(x.device):
+        ids = _per_image(ids, n, torch.int32, x.device, "resample_u8: filter")
+    return resample_launch(x, size, tuple(range(len(RESAMPLE_FILTERS))), ids, want_u8=True)[0]

@@ -101,11 +101,12 @@ def train(model, ema: ModelEMA, batches, transform, compute_loss, optimizer, gra
     return losses
 
 
-def validate(gen, batches, scale: int, *, mean, std, border: int = 4, group=None) -> dict:
+def validate(gen, batches, scale: int, *, mean, std, border: int = 4, group=None, lr_filter: str = "cv2") -> dict:
     """Validation pass: PSNR / PSNR-Y / SSIM-Y of `gen` (the EMA generator) on held-out HR crops.
 
     `batches` yields uint8 HR crops [n, 3, t, t] (t a multiple of `scale`).  Each batch goes through
-    the training degradation (data.GPUTransform: the cv2 INTER_LINEAR uint8 resize, then Normalize),
+    the training degradation (data.GPUTransform: the cv2 INTER_LINEAR uint8 resize, or with `lr_filter`
+    one of Pillow's antialiased filters / "random", then Normalize),
     the generator's inference path (eval mode, no autograd) and metrics.Evaluator, which compares
     the tanh-space output with the uint8 crop on the device; the only host read is the final one.
     The reference has no validation (its val_images.json, utils/general.py:107-111, is never read).
@@ -122,7 +123,7 @@ def validate(gen, batches, scale: int, *, mean, std, border: int = 4, group=None
         import torch.distributed as dist
         pg = None if group is True else group
         rank, world = dist.get_rank(pg), dist.get_world_size(pg)
-    transform = D.GPUTransform(scale, hr_norm=False, mean=mean, std=std, device=device)
+    transform = D.GPUTransform(scale, hr_norm=False, mean=mean, std=std, device=device, lr_filter=lr_filter)
     ev = Evaluator(device)
     was_training = g.training
     g.eval()

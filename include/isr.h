@@ -620,6 +620,64 @@ typedef struct isr_iso_noise_desc {
 } isr_iso_noise_desc;
 int isr_iso_noise(const isr_iso_noise_desc* d, isr_stream_t s);
 
+/* ---- PIL-exact resampling (LR synthesis) --------------------------------------
+ * Pillow's Image.resize on 8-bit images (Imaging/Resample.c), bit for bit: two separable passes,
+ * horizontal first, with a uint8 image between them; each pass accumulates pixel * k in int32, k
+ * the normalised double weight rounded to 22 fractional bits, from 1 << 21, then >> 22 and clip
+ * to 0..255.  On a downscale the filter's support is scaled by in/out (the antialiasing); the taps
+ * are clamped at the image edge and the shortened kernel renormalised.  Covers the reference's
+ * Random_low_rs (bicubic, antialias) and image_reader (BICUBIC / BILINEAR / BOX / NEAREST)
+ * degradations (utils/datasets.py:23-32, :218-246).
+ *
+ * The coefficient tables are made on the host, in double, in Pillow's order of operations (plain
+ * C++, no GPU): isr_resample_ksize is the taps per output pixel (0 when refused),
+ * isr_resample_tables fills bounds [out_size][2] = (first source index, tap count) and coeffs
+ * [out_size][ksize] (rows zero-padded).  NEAREST is a one-tap table (source index
+ * floor((dst + 0.5) * in / out) in Pillow's running-sum form, coefficient 1 << 22), so one kernel
+ * serves all six filters.  Refused with ISR_ERR_UNSUPPORTED: an unknown filter, a size outside
+ * [1, 16384], and a ratio in_size / out_size outside [1/8, 8] — the bound that fixes the kernel's
+ * footprint (at most ISR_RESAMPLE_MAX_KSIZE = 49 taps per axis). */
+#define ISR_RESAMPLE_NEAREST 0
+#define ISR_RESAMPLE_BOX 1
+#define ISR_RESAMPLE_BILINEAR 2
+#define ISR_RESAMPLE_HAMMING 3
+#define ISR_RESAMPLE_BICUBIC 4
+#define ISR_RESAMPLE_LANCZOS 5
+#define ISR_RESAMPLE_MAX_KSIZE 49
+int isr_resample_ksize(int filter, int in_size, int out_size);
+int isr_resample_tables(int filter, int in_size, int out_size, int32_t* bounds, int32_t* coeffs);
+
+/* isr_resample_u8: src uint8 planar [n][3][in_h][in_w] -> any non-empty subset of
+ *   dst_u8 [n][3][out_h][out_w]   the resized image q,
+ *   lr_f32 [n][3][out_h][out_w]   ((float)q / 255 - mean[c]) / std[c]  (isr_sr_transform's lr),
+ *   hr_f32 [n][3][in_h][in_w]     2x/255 - 1, or (x/255 - mean[c]) / std[c] when hr_norm
+ *                                 (isr_sr_transform's hr); only when in_h = sy * out_h and
+ *                                 in_w = sx * out_w for integers sy, sx (ISR_ERR_UNSUPPORTED else).
+ * The tables are DEVICE copies of isr_resample_tables' output for nf >= 1 filter variants, laid out
+ * bounds_* [nf][out][2], coeffs_* [nf][out][ksize_*] with one ksize per axis (rows zero-padded to
+ * it; 1 <= ksize <= 49).  filter_id (device int32 [n], or NULL = variant 0) picks each image's
+ * variant on the device; ids outside [0, nf) are clamped.  in/out per axis must lie in [1/8, 8];
+ * bounds are clamped to the image in the kernel, so a bad table gives wrong pixels, never a wild
+ * access.  One launch on `s`: no workspace, no allocation, no synchronisation.  src and dst_u8
+ * 4-byte aligned, lr_f32 and hr_f32 16-byte aligned, the tables and filter_id 4-byte aligned;
+ * n <= 65535, n*3*in_h*in_w and n*3*out_h*out_w < 2^31; dst_u8 must not be src. */
+typedef struct isr_resample_desc {
+    int32_t n, in_h, in_w, out_h, out_w;
+    int32_t nf, ksize_x, ksize_y;
+    const uint8_t* src;
+    const int32_t* bounds_x; /* device, [nf][out_w][2] */
+    const int32_t* coeffs_x; /* device, [nf][out_w][ksize_x] */
+    const int32_t* bounds_y; /* device, [nf][out_h][2] */
+    const int32_t* coeffs_y; /* device, [nf][out_h][ksize_y] */
+    const int32_t* filter_id; /* device, [n], or NULL */
+    uint8_t* dst_u8; /* or NULL */
+    float* lr_f32;   /* or NULL */
+    float* hr_f32;   /* or NULL */
+    int32_t hr_norm;
+    float mean[3], std[3];
+} isr_resample_desc;
+int isr_resample_u8(const isr_resample_desc* d, isr_stream_t s);
+
 const char* isr_last_error(void);
 int isr_version(void);
 

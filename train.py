@@ -14,7 +14,10 @@ epoch.  `--val DIR|JSON` and / or `--val_synthetic N` (with `--val_shape`, `--va
 the EMA generator after an epoch in `--resnet` and SRGAN mode (trainer.validate: PSNR, PSNR-Y, SSIM-Y
 on the device): one printed line, val/* scalars, a line in work_dir/val_<save_name>.jsonl, a `val`
 entry in the checkpoint and a copy of it as <checkpoint stem>.best.pt when PSNR-Y improved; without
-these flags nothing changes.  Every mode trains on the HIP path: ResNet (train-mode BatchNorm kernels)
+these flags nothing changes.  `--lr_filter` chooses how the LR image is made from the HR crop, for
+training and validation: cv2 (the default, SR_dataset's INTER_LINEAR without antialiasing), one of
+Pillow's antialiased filters (bicubic, ...: Image.resize bit for bit, one HIP launch) or random
+(image_reader's per-sample mix); the val_*.jsonl line records it.  Every mode trains on the HIP path: ResNet (train-mode BatchNorm kernels)
 and EResNet (`--enchant`) in `--resnet` pixel-loss mode and in SRGAN mode (VGG
 perceptual + adversarial, discriminator on libisr), and the Denoise model
 (`--train_denoise`).
@@ -118,6 +121,11 @@ def val_batches(opt, device) -> list:
     return list(crops.split(opt.batch_size))
 
 
+def lr_filter_of(opt) -> str:
+    """--lr_filter of a parsed command line; "cv2" (SR_dataset's resize) when the flag was not given."""
+    return getattr(opt, "lr_filter", "cv2")
+
+
 class _Validation:
     """Validation after every --val_every-th epoch: trainer.validate on the EMA generator; rank 0
     prints one line, logs val/* scalars, appends a JSON line to val_<save_name>.jsonl, and the
@@ -141,8 +149,8 @@ class _Validation:
             return
         t0 = time.perf_counter()
         res = trainer.validate(ema.ema, self.batches, self.opt.scale, mean=self.mean, std=self.std,
-                               group=self.group)
-        res = dict(epoch=epoch, **res, seconds=round(time.perf_counter() - t0, 4))
+                               group=self.group, lr_filter=lr_filter_of(self.opt))
+        res = dict(epoch=epoch, **res, seconds=round(time.perf_counter() - t0, 4), lr_filter=lr_filter_of(self.opt))
         self.entry = res
         if self.rank != 0:
             return
@@ -319,7 +327,8 @@ def main(opt):
     if opt.resnet:
         model, ema, compute_loss, optimizer, schedule, start = setup_resnet(opt, device, group, iters, res_ck)
         print(f"Train: ResNet {opt.epochs} epochs, {sum(p.numel() for p in model.parameters()):,} parameters")
-        transform = data.GPUTransform(opt.scale, hr_norm=False, mean=mean, std=std, device=device)
+        transform = data.GPUTransform(opt.scale, hr_norm=False, mean=mean, std=std, device=device,
+                                      lr_filter=lr_filter_of(opt), seed=opt.seed + rank)
         val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, res_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train(model, ema, batches, transform, compute_loss, optimizer, scaler_gen, schedule,
@@ -339,7 +348,8 @@ def main(opt):
             setup_srgan(opt, device, group, iters, gen_ck, res_ck)
         print(f"Train: {opt.epochs} epochs, gen {sum(p.numel() for p in gen_net.parameters()):,} parameters, "
               f"dis {sum(p.numel() for p in dis_net.parameters()):,} parameters")
-        transform = data.GPUTransform(opt.scale, hr_norm=True, mean=mean, std=std, device=device)
+        transform = data.GPUTransform(opt.scale, hr_norm=True, mean=mean, std=std, device=device,
+                                      lr_filter=lr_filter_of(opt), seed=opt.seed + rank)
         val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, gen_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train_srgan(gen_net, ema, dis_net, batches, transform, compute_loss, optimizer_g,
@@ -408,9 +418,18 @@ def parse(argv=None):
     p.add_argument("--val_shape", type=int, default=512, help="HR centre crop of the validation images (rounded up "
                    "to the scale; smaller images are skipped)")
     p.add_argument("--val_every", type=int, default=1, help="validate after every E-th epoch")
+    # no default in the namespace: a run without the flag parses to exactly what it did before the flag
+    # existed (lr_filter_of reads it, "cv2" when absent)
+    p.add_argument("--lr_filter", default=argparse.SUPPRESS, choices=data.GPUTransform.LR_FILTERS,
+                   help="how the LR image is made from the HR crop, for training and for the validation pass: cv2 "
+                   "(the reference SR_dataset's INTER_LINEAR without antialiasing), one of Pillow's antialiased "
+                   "resampling filters (bit-exact Image.resize; bicubic is the usual SR benchmark degradation), or "
+                   "random (the reference image_reader's per-sample mix of bicubic / bilinear / box / nearest)")
     opt = p.parse_args(argv)
     if opt.val_every < 1:
         p.error("--val_every must be at least 1")
+    if lr_filter_of(opt) != "cv2" and opt.train_denoise:
+        p.error("--lr_filter chooses the super-resolution LR model; --train_denoise has no LR image")
     if not opt.data and Path("train_images.json").is_file():
         opt.data = "train_images.json"
     if opt.steps == 0:
