@@ -31,9 +31,11 @@ from dataclasses import dataclass, field
 import torch
 
 from . import ops
-from .discriminator import expand_fwd
+from ._lib import load as _load_lib
 from .engine import PackedConv, _fold, _pack3
 from .ops import ActBuffer, round_up
+from .train_layers import (PlanLease, TrainConv, bn_backward_step, bn_forward_step, expand_fwd,
+                           gather_wgrad)
 
 SLOPE = 0.2  # every activation of Denoise is LeakyReLU(0.2) (utils/models.py:676-690)
 
@@ -82,7 +84,7 @@ class DenoisePlan:
             raise ValueError(f"Denoise needs an even input size (stride-2 conv + PixelShuffle(2) restore it), "
                              f"got {h}x{w}")
         self.key = (n, h, w, str(device))
-        lib = ops._lib.load()
+        lib = _load_lib()
         h2, w2 = h // 2, w // 2
         ha2, wa2 = round_up(h2, ops.TILE_H), round_up(w2, ops.TILE_W)
         # full-resolution 64-channel buffers read by the stride-2 conv need pad 2 and
@@ -155,45 +157,11 @@ def run_denoise(dw: DenoiseWeights, x: torch.Tensor) -> torch.Tensor:
 
 
 # ===================================================================== training
-class _TLayer:
-    """One conv of the Denoise network in training: parameter refs + packed copies."""
-
-    def __init__(self, conv_mod, kind: str):
-        self.mod = conv_mod                      # reference Conv / ConvWithoutBN
-        self.w = conv_mod.conv.weight
-        self.b = conv_mod.conv.bias
-        bn = getattr(conv_mod, "bn", None)
-        self.bn = bn if isinstance(bn, torch.nn.BatchNorm2d) else None
-        self.kind = kind                         # "3x3", "s2" (stride 2), "head", "tail"
-        self.cout, self.cin = self.w.shape[:2]
-        self.fwd = self.bwd = None
-        self.bn_state = None
-
-    def params(self) -> list[torch.Tensor]:
-        out = [self.w] + ([self.b] if self.b is not None else [])
-        return out + ([self.bn.weight, self.bn.bias] if self.bn is not None else [])
-
-    def pack(self) -> None:
-        w = self.w.detach().float()
-        if self.kind == "3x3":
-            self.fwd = ops.pack_conv3x3(w, out=self.fwd)
-            self.bwd = ops.pack_conv3x3_dgrad(w, out=self.bwd)
-        elif self.kind == "s2":
-            from .discriminator import expand_dgrad
-            self.fwd = ops.pack_conv3x3(expand_fwd(w), out=self.fwd)
-            self.bwd = ops.pack_conv3x3(expand_dgrad(w), out=self.bwd)
-        elif self.kind == "head":
-            self.fwd = ops.pack_head9x9(w, out=self.fwd)
-        else:  # tail: its input gradient is a head9x9 conv with 180°-rotated, transposed weights
-            self.fwd = ops.pack_tail9x9(w, out=self.fwd)
-            self.bwd = ops.pack_head9x9(w.flip(2, 3).transpose(0, 1).contiguous(), out=self.bwd)
-
-
 class _TBlock:
     """ResidualBlock1 (utils/models.py:202-209) with its saved activations."""
 
     def __init__(self, blk, n, h, w, c, dev, ha, wa, out_sub: dict):
-        self.a, self.b = _TLayer(blk.m[0], "3x3"), _TLayer(blk.m[1], "3x3")
+        self.a, self.b = TrainConv.of(blk.m[0], "3x3"), TrainConv.of(blk.m[1], "3x3")
         self.Za = ActBuffer.alloc(n, h, w, c, 0, dev, ha=ha, wa=wa)
         self.Ha = ActBuffer.alloc(n, h, w, c, 1, dev, ha=ha, wa=wa)
         self.Zb = ActBuffer.alloc(n, h, w, c, 0, dev, ha=ha, wa=wa)
@@ -212,7 +180,7 @@ class DenoiseTrainPlan:
     gradient, wgrad(Ha), dgrad with LeakyReLU'(Ha) in the epilogue, BN_a backward,
     wgrad(X), dgrad + the skip gradient (r1) → the block-input gradient.  The
     stride-2 conv: wgrad over the x_sub2 view (taps {0,1}²) gathered to 3x3, dgrad
-    as the 2x2-tap conv with the PixelShuffle store (discriminator.py); the
+    as the 2x2-tap conv with the PixelShuffle store (train_layers.py); the
     PixelShuffle + LeakyReLU: isr_pixel_unshuffle2 with the LeakyReLU' mask;
     the tail: tanh' then wgrad9x9 and a head9x9 dgrad; the head: wgrad9x9 on the
     masked trunk gradient (ew_combine of chain + trunk)."""
@@ -227,10 +195,10 @@ class DenoiseTrainPlan:
         h2, w2 = h // 2, w // 2
         ha2, wa2 = round_up(h2, ops.TILE_H), round_up(w2, ops.TILE_W)
         sub = dict(min_hp=2 * ha2 + 4, min_wp=2 * wa2 + 4)
-        self.head = _TLayer(model.conv0[0], "head")
-        self.down = _TLayer(model.residual_conv0, "s2")
-        self.conv1 = _TLayer(model.conv1, "3x3")
-        self.tail = _TLayer(model.conv2[0], "tail")
+        self.head = TrainConv.of(model.conv0[0], "head")
+        self.down = TrainConv.of(model.residual_conv0, "s2")
+        self.conv1 = TrainConv.of(model.conv1, "3x3")
+        self.tail = TrainConv.of(model.conv2[0], "tail")
         if self.conv1.bn is None:
             raise NotImplementedError("Denoise training expects an unfused model (Conv layers with BatchNorm)")
         self.conv1.bn_state = ops.BNState(64, dev)
@@ -259,46 +227,36 @@ class DenoiseTrainPlan:
             l.pack()
 
     # ----------------------------------------------------------------- forward
-    @staticmethod
-    def _bn_fwd(l: _TLayer, z: ActBuffer, y: ActBuffer, c: int, **kw) -> None:
-        ops.bn_forward(ops.bn_desc(z, y, c, l.bn_state, l.bn, **kw), l.bn_state)
-        if l.bn.num_batches_tracked is not None:
-            l.bn.num_batches_tracked.add_(1)
-
     def _chain_fwd(self, blocks, x: ActBuffer, c: int) -> ActBuffer:
         for b in blocks:
             ops.conv3x3(x, c, b.a.fwd, None, c, b.Za, slope=1.0)
-            self._bn_fwd(b.a, b.Za, b.Ha, c, slope=SLOPE)
+            bn_forward_step(b.a, b.Za, b.Ha, slope=SLOPE)
             ops.conv3x3(b.Ha, c, b.b.fwd, None, c, b.Zb, slope=1.0)
-            self._bn_fwd(b.b, b.Zb, b.Y, c, slope=1.0, r1=x, s1=1.0)
+            bn_forward_step(b.b, b.Zb, b.Y, slope=1.0, r1=x, s1=1.0)
             x = b.Y
         return x
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self.x = x = x.float().contiguous()
-        ops.head9x9(x, self.head.fwd, self.head.b.detach(), self.F, slope=SLOPE)
+        ops.head9x9(x, self.head.fwd, self.head.bias, self.F, slope=SLOPE)
         self.x_last0 = self._chain_fwd(self.res0, self.F, 64)
-        ops.conv3x3(self.x_last0, 256, self.down.fwd, self.down.b.detach(), 256, self.Q0, slope=SLOPE,
+        ops.conv3x3(self.x_last0, 256, self.down.fwd, self.down.bias, 256, self.Q0, slope=SLOPE,
                     x_sub2=True, taps=1)
         self.q_last = self._chain_fwd(self.res1, self.Q0, 256)
         ops.pixel_shuffle2(self.S, self.q_last, 64, slope=SLOPE)
         self.r_last = self._chain_fwd(self.res2, self.S, 64)
         ops.conv3x3(self.r_last, 64, self.conv1.fwd, None, 64, self.Z1, slope=1.0)
-        self._bn_fwd(self.conv1, self.Z1, self.T, 64, slope=1.0, r1=self.F, s1=1.0)
+        bn_forward_step(self.conv1, self.Z1, self.T, slope=1.0, r1=self.F, s1=1.0)
         y = torch.empty(self.out_shape, device=self.device)
-        ops.tail9x9(self.T, self.tail.fwd, self.tail.b.detach(), y)
+        ops.tail9x9(self.T, self.tail.fwd, self.tail.bias, y)
         self.y = y
         return y
 
     # ----------------------------------------------------------------- backward
-    def _bn_bwd(self, l: _TLayer, z: ActBuffer, g: ActBuffer, dz: ActBuffer, c: int, grads: dict) -> None:
-        dgam = torch.empty(c, device=self.device)
-        dbet = torch.empty(c, device=self.device)
-        ops.bn_backward(ops.bn_desc(z, g, c, l.bn_state, l.bn, dz=dz, dgamma=dgam, dbeta=dbet,
-                                    update_running=False), l.bn_state)
-        grads[id(l.bn.weight)], grads[id(l.bn.bias)] = dgam, dbet
+    def _bn_bwd(self, l: TrainConv, z: ActBuffer, g: ActBuffer, dz: ActBuffer, grads: dict) -> None:
+        grads[id(l.bn.weight)], grads[id(l.bn.bias)] = bn_backward_step(l, z, g, dz, self.device)
 
-    def _wgrad(self, l: _TLayer, x: ActBuffer, g: ActBuffer, grads: dict) -> None:
+    def _wgrad(self, l: TrainConv, x: ActBuffer, g: ActBuffer, grads: dict) -> None:
         dw = torch.empty(l.cout, l.cin, 3, 3, device=self.device)
         ops.wgrad3x3(x, l.cin, g, l.cout, dw, None)
         grads[id(l.w)] = dw
@@ -312,10 +270,10 @@ class DenoiseTrainPlan:
             b = blocks[i]
             xi = blocks[i - 1].Y if i > 0 else x_in
             dz, gh, gin = [p for p in pool if p is not g][:3]
-            self._bn_bwd(b.b, b.Zb, g, dz, c, grads)
+            self._bn_bwd(b.b, b.Zb, g, dz, grads)
             self._wgrad(b.b, b.Ha, dz, grads)
             ops.conv3x3(dz, c, b.b.bwd, None, c, gh, slope=1.0, m=b.Ha, mslope=SLOPE)
-            self._bn_bwd(b.a, b.Za, gh, dz, c, grads)
+            self._bn_bwd(b.a, b.Za, gh, dz, grads)
             self._wgrad(b.a, xi, dz, grads)
             mk = dict(m=m_in, mslope=SLOPE) if (i == 0 and m_in is not None) else {}
             ops.conv3x3(dz, c, b.a.bwd, None, c, gin, slope=1.0, r1=g, s1=1.0, **mk)
@@ -325,7 +283,6 @@ class DenoiseTrainPlan:
         return g
 
     def backward(self, gy: torch.Tensor) -> dict:
-        from .discriminator import gather_wgrad
         dev = self.device
         grads: dict = {}
         gp = (gy.float() * (1.0 - self.y * self.y)).contiguous()  # tanh' (utils/models.py:692, act=nn.Tanh())
@@ -338,7 +295,7 @@ class DenoiseTrainPlan:
         ops.head9x9(gp, self.tail.bwd, None, gT, slope=1.0)
         # conv1 (+BN) — gT also reaches F through the trunk residual
         f0, f1 = pool[0], pool[1]
-        self._bn_bwd(self.conv1, self.Z1, gT, f0, 64, grads)
+        self._bn_bwd(self.conv1, self.Z1, gT, f0, grads)
         self._wgrad(self.conv1, self.r_last, f0, grads)
         ops.conv3x3(f0, 64, self.conv1.bwd, None, 64, f1, slope=1.0)
         # residual_2, then PixelShuffle(2) + LeakyReLU backward into the half grid
@@ -369,15 +326,15 @@ class _DenoiseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, plan, *params):
         y = plan.forward(x)
-        ctx.plan = plan
-        plan.busy = True
-        return y
+        ctx.lease = PlanLease(plan)
+        # an alias: the plan keeps y itself for tanh', and must not hold the graph that holds its lease
+        return y.detach()
 
     @staticmethod
     def backward(ctx, gy):
-        plan = ctx.plan
+        plan = ctx.lease.plan
         grads = plan.backward(gy.contiguous())
-        plan.busy = False
+        ctx.lease.release()
         out = [grads.get(id(p)) for p in plan.params()]
         if plan.grad_group is not None:  # data parallel: one flat RCCL all-reduce (mean), as DDP
             from .train_engine import allreduce_mean
@@ -388,7 +345,7 @@ class _DenoiseFn(torch.autograd.Function):
 def train_forward(model, x: torch.Tensor) -> torch.Tensor:
     """Differentiable train-mode Denoise forward on libisr (train.py:52-63 with
     --train_denoise).  One plan per input geometry; the graph of one call must be
-    backpropagated before the next call (the plan holds its activations)."""
+    backpropagated or dropped before the next call (the plan holds its activations)."""
     n, _, h, w = x.shape
     key = (n, h, w, str(x.device))
     plan = model.__dict__.get("_isr_train_plan")

@@ -4,24 +4,13 @@
 stride 2 on every second block — forward and backward, in train mode.  The
 adaptive pool and the two Linear layers (≈0.6 GFLOP) stay torch ops.
 
-Stride 2 on the stride-1 kernel, exactly (no zero taps beyond a 2x2 window):
-  forward   out(y,x) = Σ W[dy][dx] in(2y+dy-1, 2x+dx-1)  is a conv over the
-            PixelUnshuffle'd input (x_sub2 view: channel s*cin + c = in[c] at
-            (2y'+a, 2x'+b), s = 2a+b) with phase-expanded weights
-            W'[co][s*cin+c][ty][tx] = W[co][c][2ty+a-1][2tx+b-1] on taps {0,1}²;
-  dgrad     dx(c, 2y'+a, 2x'+b) is a conv over dz with 4*cin outputs
-            W''[4c+s][co][ty][tx] = W[co][c][dy][dx] on taps {1,2}²
-            (a=0: ty=1↔dy=1; a=1: ty=2↔dy=0, ty=1↔dy=2), stored through the
-            PixelShuffle(2) epilogue;
-  wgrad     over the x_sub2 view on taps {0,1}² (isr_wgrad_desc.x_sub2 / taps),
-            dW gathered from dW'.
+Stride 2 runs on the stride-1 kernel through the 2x2 phase decomposition (train_layers.py).
 The first layer's 3 input channels are zero-padded to 32 (the wgrad K tile).
 Activations are bf16 channel-blocked (ops.ActBuffer), accumulation fp32, BN
 statistics in double (isr_bn_*).
 """
 from __future__ import annotations
 
-import ctypes
 import os as _os
 
 import torch
@@ -30,68 +19,13 @@ from torch import nn
 from . import ops
 from ._lib import load as _load_lib
 from .ops import ActBuffer, round_up
+from .train_layers import (PlanLease, TrainConv, bn_backward_step, bn_forward_step,  # noqa: F401
+                           expand_dgrad, expand_fwd, gather_wgrad)
 
 SLOPE = 0.2
 
-
-def expand_fwd(w: torch.Tensor) -> torch.Tensor:
-    """W [co][ci][3][3] → W' [co][4ci][3][3] for the x_sub2 conv on taps {0,1}²."""
-    co, ci = w.shape[:2]
-    out = torch.zeros(co, 4 * ci, 3, 3, device=w.device, dtype=torch.float32)
-    # phase a: (ty, dy) pairs with dy = 2ty + a - 1 in [0, 2]
-    pairs = {0: [(1, 1)], 1: [(0, 0), (1, 2)]}
-    for a in (0, 1):
-        for b in (0, 1):
-            s = 2 * a + b
-            for ty, dy in pairs[a]:
-                for tx, dx in pairs[b]:
-                    out[:, s * ci:(s + 1) * ci, ty, tx] = w[:, :, dy, dx]
-    return out
-
-
-def expand_dgrad(w: torch.Tensor) -> torch.Tensor:
-    """W [co][ci][3][3] → W'' [4ci][co][3][3] (output channel 4c+s) on taps {1,2}²."""
-    co, ci = w.shape[:2]
-    out = torch.zeros(ci, 4, co, 3, 3, device=w.device, dtype=torch.float32)
-    pairs = {0: [(1, 1)], 1: [(2, 0), (1, 2)]}  # (ty, dy)
-    wt = w.transpose(0, 1)  # [ci][co][3][3]
-    for a in (0, 1):
-        for b in (0, 1):
-            s = 2 * a + b
-            for ty, dy in pairs[a]:
-                for tx, dx in pairs[b]:
-                    out[:, s, :, ty, tx] = wt[:, :, dy, dx]
-    return out.reshape(4 * ci, co, 3, 3).contiguous()
-
-
-def gather_wgrad(dwp: torch.Tensor, ci: int) -> torch.Tensor:
-    """dW' [co][4ci][3][3] (wgrad over the unshuffled input) → dW [co][ci][3][3]."""
-    co = dwp.shape[0]
-    dw = torch.empty(co, ci, 3, 3, device=dwp.device, dtype=dwp.dtype)
-    ty_a = {0: (0, 1), 1: (1, 0), 2: (1, 1)}  # dy → (ty, a)
-    for dy in range(3):
-        ty, a = ty_a[dy]
-        for dx in range(3):
-            tx, b = ty_a[dx]
-            s = 2 * a + b
-            dw[:, :, dy, dx] = dwp[:, s * ci:(s + 1) * ci, ty, tx]
-    return dw
-
-
 # ISR_DISC_REUSE=0: always recompute (A/B)
 REUSE = _os.environ.get("ISR_DISC_REUSE", "1") == "1"
-
-
-class _Layer:
-    def __init__(self, block: nn.Module):
-        conv = block.conv
-        self.w, self.b = conv.weight, conv.bias
-        self.bn = getattr(block, "bn", None)
-        self.cin, self.cout = conv.in_channels, conv.out_channels
-        self.stride = conv.stride[0]
-        self.cin_p = 32 if self.cin < 32 else self.cin  # first layer: 3 → 32 zero-padded channels (wgrad K tile)
-        self.fwd = self.bwd = None
-        self.bn_state = None
 
 
 class DiscriminatorPlan:
@@ -100,8 +34,8 @@ class DiscriminatorPlan:
     def __init__(self, dis: nn.Module, n: int, h: int, w: int, device):
         self.key = (n, h, w, str(device))
         self.device = dev = torch.device(device)
-        self.layers = [_Layer(b) for b in dis.conv_blocks]
-        L = self.layers
+        # first layer: 3 → 32 zero-padded input channels (wgrad K tile)
+        L = self.layers = [TrainConv.of(b, cin_p=max(b.conv.in_channels, 32)) for b in dis.conv_blocks]
         if L[0].stride != 1 or any(l.bn is None for l in L[1:]) or L[0].bn is not None:
             raise NotImplementedError("DiscriminatorPlan expects the reference block layout")
         if any(l.cin_p % 16 or l.cout % 64 for l in L):
@@ -149,14 +83,7 @@ class DiscriminatorPlan:
 
     # ----------------------------------------------------------------- weights
     def params(self) -> list[torch.Tensor]:
-        out = []
-        for l in self.layers:
-            out.append(l.w)
-            if l.b is not None:
-                out.append(l.b)
-            if l.bn is not None:
-                out += [l.bn.weight, l.bn.bias]
-        return out
+        return [p for l in self.layers for p in l.params()]
 
     def pack(self) -> None:
         # repack only when a weight changed since this plan's last pack (an SRGAN step runs three
@@ -166,16 +93,7 @@ class DiscriminatorPlan:
             return
         self._pack_key = key
         for l in self.layers:
-            w = l.w.detach().float()
-            if l.cin_p != l.cin:
-                w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, l.cin_p - l.cin))
-            if l.stride == 2:
-                l.fwd = ops.pack_conv3x3(expand_fwd(w), out=l.fwd)
-                l.bwd = ops.pack_conv3x3(expand_dgrad(w), out=l.bwd)
-            else:
-                l.fwd = ops.pack_conv3x3(w, out=l.fwd)
-                wb = w if l.cin_p % 32 == 0 else torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 32 - l.cin_p % 32))
-                l.bwd = ops.pack_conv3x3_dgrad(wb, out=l.bwd)
+            l.pack()
 
     # ----------------------------------------------------------------- forward
     def _input_key(self, x: torch.Tensor):
@@ -199,7 +117,7 @@ class DiscriminatorPlan:
             for l, d in zip(self.layers, self._bn_descs):
                 if l.bn is not None:
                     l.bn_state.acc.copy_(l.fwd_acc)
-                    ops.check(ops._lib.load().isr_bn_finalize(ctypes.byref(d), ops._stream()), "isr_bn_finalize")
+                    ops.bn_finalize(d)
                     if l.bn.num_batches_tracked is not None:
                         l.bn.num_batches_tracked.add_(1)
             return ops.blocked_to_nchw(self.A[-1], torch.empty(self.feat_shape, device=self.device))
@@ -208,23 +126,19 @@ class DiscriminatorPlan:
         ops.nchw_to_blocked(x.float().contiguous(), self.xin)
         prev = self.xin
         for i, l in enumerate(self.layers):
-            bias = l.b.detach() if l.b is not None else None
             y = self.A[i] if l.bn is None else self.Z[i]
             if l.stride == 2:
-                ops.conv3x3(prev, 4 * l.cin, l.fwd, bias, l.cout, y, slope=1.0 if l.bn is not None else SLOPE,
+                ops.conv3x3(prev, 4 * l.cin, l.fwd, l.bias, l.cout, y, slope=1.0 if l.bn is not None else SLOPE,
                             x_sub2=True, taps=1)
             else:
-                ops.conv3x3(prev, l.cin_p, l.fwd, bias, l.cout, y, slope=1.0 if l.bn is not None else SLOPE)
+                ops.conv3x3(prev, l.cin_p, l.fwd, l.bias, l.cout, y, slope=1.0 if l.bn is not None else SLOPE)
             d = None
             if l.bn is not None:
-                d = ops.bn_desc(self.Z[i], self.A[i], l.cout, l.bn_state, l.bn, slope=SLOPE)
-                ops.bn_forward(d, l.bn_state)
+                d = bn_forward_step(l, self.Z[i], self.A[i], slope=SLOPE)
                 if REUSE:
                     if getattr(l, "fwd_acc", None) is None:
                         l.fwd_acc = torch.empty_like(l.bn_state.acc)
                     l.fwd_acc.copy_(l.bn_state.acc)  # this batch's sums, for a replayed running update
-                if l.bn.num_batches_tracked is not None:
-                    l.bn.num_batches_tracked.add_(1)
             self._bn_descs.append(d)
             prev = self.A[i]
         return ops.blocked_to_nchw(self.A[-1], torch.empty(self.feat_shape, device=self.device))
@@ -247,10 +161,7 @@ class DiscriminatorPlan:
             gw = []
             g = self.gA[i]
             if l.bn is not None:
-                dgam = torch.empty(l.cout, device=self.device)
-                dbet = torch.empty(l.cout, device=self.device)
-                ops.bn_backward(ops.bn_desc(self.Z[i], g, l.cout, l.bn_state, l.bn, dz=self.dZ[i], dgamma=dgam,
-                                            dbeta=dbet, update_running=False), l.bn_state)
+                dgam, dbet = bn_backward_step(l, self.Z[i], g, self.dZ[i], self.device)
                 g = self.dZ[i]
             xin = self.A[i - 1] if i > 0 else self.xin
             # weight (+ bias) gradient
@@ -290,27 +201,11 @@ class DiscriminatorPlan:
         return dx, out
 
 
-class _Lease:
-    """Holds a plan (its saved activations) until the backward ran or the graph died."""
-
-    def __init__(self, plan: DiscriminatorPlan):
-        self.plan = plan
-        plan.busy = True
-
-    def release(self):
-        if self.plan is not None:
-            self.plan.busy = False
-            self.plan = None
-
-    def __del__(self):
-        self.release()
-
-
 class _DiscFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, plan, *params):
         out = plan.forward(x)
-        ctx.lease = _Lease(plan)
+        ctx.lease = PlanLease(plan)
         return out
 
     @staticmethod

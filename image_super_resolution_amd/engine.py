@@ -25,7 +25,7 @@ from dataclasses import dataclass, field
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .ops import ActBuffer
 
 LEAKY_DEFAULT = 0.01
@@ -217,7 +217,7 @@ class GeneratorPlan:
         self.bufs = bufs
         feat = bufs.feat
         X, Y, Z = bufs.dense
-        lib = ops._lib.load()
+        lib = _lib.load()
         conv, head, tail = lib.isr_conv3x3_fwd, lib.isr_head9x9_fwd, lib.isr_tail9x9_fwd
         conv_wino = lib.isr_conv3x3_wino_fwd
         dummy_x = torch.empty((n, 3, h, w), dtype=torch.uint8 if x_u8 else torch.float32, device=device)
@@ -323,7 +323,7 @@ class ConvChain:
                  state: torch.Tensor | None = None):
         """`state`: share another chain's state words (chains launched one after another on one
         stream: generations and progress words are serial, and one give-up count guards both)."""
-        lib = ops._lib.load()
+        lib = _lib.load()
         kinds = []
         g = descs[0].x
         for d in descs:
@@ -375,7 +375,7 @@ class ConvChain:
             self.state = state
         else:
             self.state = torch.zeros(words, dtype=torch.int32, device=device)
-        self.desc = ops._lib.IsrChainDesc(self._table.data_ptr(), self._kinds.data_ptr(), len(descs), grid.n,
+        self.desc = _lib.IsrChainDesc(self._table.data_ptr(), self._kinds.data_ptr(), len(descs), grid.n,
                                           grid.ha, grid.wa, self.state.data_ptr(), int(acquire), grid.f16)
         self.nl = len(descs)
         self.fn = lib.isr_conv_chain

@@ -137,22 +137,28 @@ def _wdtype(f16: bool) -> torch.dtype:
     return torch.float16 if f16 else torch.bfloat16
 
 
-def pack_conv3x3(w: torch.Tensor, out: torch.Tensor | None = None, f16: bool = False) -> torch.Tensor:
-    """fp32 OIHW [cout, cin, 3, 3] device weights → packed bf16 (fp16 with `f16`: the
-    inference forward, isr_pack_conv3x3_f16) kernel layout."""
-    _require_gpu(w, "pack_conv3x3")
+def _pack(what: str, w: torch.Tensor, out: torch.Tensor | None, dt: torch.dtype, sizer: str, entry: str,
+          label: str | None = None) -> torch.Tensor:
+    """The pack wrappers' common body: check the device, size the output, check or allocate
+    `out`, call the library's `entry`."""
+    _require_gpu(w, what)
     lib = _lib.load()
     cout, cin = w.shape[:2]
     w = w.detach().float().contiguous()
-    n = lib.isr_conv3x3_packed_bytes(cout, cin) // 2
-    dt = _wdtype(f16)
+    n = getattr(lib, sizer)(cout, cin) // 2
     if out is None:
         out = torch.empty(n, dtype=dt, device=w.device)
     elif out.numel() != n or out.dtype != dt:
-        raise ValueError("pack_conv3x3: bad output buffer")
-    fn = lib.isr_pack_conv3x3_f16 if f16 else lib.isr_pack_conv3x3
-    check(fn(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "isr_pack_conv3x3")
+        raise ValueError(f"{what}: bad output buffer")
+    check(getattr(lib, entry)(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), label or "isr_" + what)
     return out
+
+
+def pack_conv3x3(w: torch.Tensor, out: torch.Tensor | None = None, f16: bool = False) -> torch.Tensor:
+    """fp32 OIHW [cout, cin, 3, 3] device weights → packed bf16 (fp16 with `f16`: the
+    inference forward, isr_pack_conv3x3_f16) kernel layout."""
+    return _pack("pack_conv3x3", w, out, _wdtype(f16), "isr_conv3x3_packed_bytes",
+                 "isr_pack_conv3x3_f16" if f16 else "isr_pack_conv3x3")
 
 
 def pack_conv3x3_dgrad(w: torch.Tensor, scale: float = 1.0, sub2: bool = False,
@@ -207,35 +213,13 @@ def pack_batch(table: tuple[torch.Tensor, int]) -> None:
 
 
 def pack_head9x9(w: torch.Tensor, out: torch.Tensor | None = None, f16: bool = False) -> torch.Tensor:
-    _require_gpu(w, "pack_head9x9")
-    lib = _lib.load()
-    cout, cin = w.shape[:2]
-    w = w.detach().float().contiguous()
-    n = lib.isr_head9x9_packed_bytes(cout, cin) // 2
-    dt = _wdtype(f16)
-    if out is None:
-        out = torch.empty(n, dtype=dt, device=w.device)
-    elif out.numel() != n or out.dtype != dt:
-        raise ValueError("pack_head9x9: bad output buffer")
-    fn = lib.isr_pack_head9x9_f16 if f16 else lib.isr_pack_head9x9
-    check(fn(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "isr_pack_head9x9")
-    return out
+    return _pack("pack_head9x9", w, out, _wdtype(f16), "isr_head9x9_packed_bytes",
+                 "isr_pack_head9x9_f16" if f16 else "isr_pack_head9x9")
 
 
 def pack_tail9x9(w: torch.Tensor, out: torch.Tensor | None = None, f16: bool = False) -> torch.Tensor:
-    _require_gpu(w, "pack_tail9x9")
-    lib = _lib.load()
-    cout, cin = w.shape[:2]
-    w = w.detach().float().contiguous()
-    n = lib.isr_tail9x9_packed_bytes(cout, cin) // 2
-    dt = _wdtype(f16)
-    if out is None:
-        out = torch.empty(n, dtype=dt, device=w.device)
-    elif out.numel() != n or out.dtype != dt:
-        raise ValueError("pack_tail9x9: bad output buffer")
-    fn = lib.isr_pack_tail9x9_f16 if f16 else lib.isr_pack_tail9x9
-    check(fn(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "isr_pack_tail9x9")
-    return out
+    return _pack("pack_tail9x9", w, out, _wdtype(f16), "isr_tail9x9_packed_bytes",
+                 "isr_pack_tail9x9_f16" if f16 else "isr_pack_tail9x9")
 
 
 # ---------------------------------------------------------------- launches
@@ -294,18 +278,8 @@ def conv3x3(x: ActBuffer, cin: int, wpack: torch.Tensor, bias: torch.Tensor | No
 def pack_conv3x3_wino(w: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """fp32 OIHW [cout, cin, 3, 3] device weights → the fp16 Winograd F(2,3) pack of
     isr_conv3x3_wino_fwd (12 transformed values per (cout, cin), layout in include/isr.h)."""
-    _require_gpu(w, "pack_conv3x3_wino")
-    lib = _lib.load()
-    cout, cin = w.shape[:2]
-    w = w.detach().float().contiguous()
-    n = lib.isr_conv3x3_wino_packed_bytes(cout, cin) // 2
-    if out is None:
-        out = torch.empty(n, dtype=torch.float16, device=w.device)
-    elif out.numel() != n or out.dtype != torch.float16:
-        raise ValueError("pack_conv3x3_wino: bad output buffer")
-    check(lib.isr_pack_conv3x3_wino_f16(w.data_ptr(), out.data_ptr(), cout, cin, _stream()),
-          "isr_pack_conv3x3_wino_f16")
-    return out
+    return _pack("pack_conv3x3_wino", w, out, torch.float16, "isr_conv3x3_wino_packed_bytes",
+                 "isr_pack_conv3x3_wino_f16", "isr_pack_conv3x3_wino_f16")
 
 
 def launch_conv3x3_wino(d: IsrConvDesc) -> None:
@@ -642,6 +616,12 @@ def bn_forward(d: _lib.IsrBnDesc, st: BNState) -> None:
     check(lib.isr_bn_stats(ctypes.byref(d), s), "isr_bn_stats")
     check(lib.isr_bn_finalize(ctypes.byref(d), s), "isr_bn_finalize")
     check(lib.isr_bn_apply(ctypes.byref(d), s), "isr_bn_apply")
+
+
+def bn_finalize(d: _lib.IsrBnDesc) -> None:
+    """The running-statistics update alone, from the batch sums in the descriptor's acc (a
+    replayed forward: discriminator.DiscriminatorPlan.forward)."""
+    check(_lib.load().isr_bn_finalize(ctypes.byref(d), _stream()), "isr_bn_finalize")
 
 
 def bn_backward(d: _lib.IsrBnDesc, st: BNState) -> None:

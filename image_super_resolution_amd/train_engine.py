@@ -31,7 +31,6 @@ from __future__ import annotations
 import os as _os
 
 import ctypes
-from dataclasses import dataclass
 
 import torch
 import torch.distributed as dist
@@ -40,51 +39,15 @@ from torch import nn
 from . import _lib, ops
 from ._lib import load as _load_lib
 from .ops import ActBuffer
+from .train_layers import TrainConv
 
 LEAKY = 0.01
 
 
-@dataclass
-class TConv:
-    """One conv layer of the generator: parameter references + packed copies."""
-    w: torch.Tensor
-    b: torch.Tensor | None
-    cin: int
-    cout: int
-    kind: str                  # "3x3", "head", "tail"
-    dgrad_scale: float = 1.0
-    sub2: bool = False         # dgrad reads the PixelShuffle'd gradient (Scaler)
-    fwd: torch.Tensor | None = None
-    bwd: torch.Tensor | None = None
-    bn: nn.Module | None = None          # train-mode BatchNorm2d after the conv (ResNet's Conv)
-    bn_state: object | None = None
-
-    def pack(self):
-        w = self.w.detach()
-        if self.kind == "3x3":
-            self.fwd = ops.pack_conv3x3(w, out=self.fwd)
-            self.bwd = ops.pack_conv3x3_dgrad(w, scale=self.dgrad_scale, sub2=self.sub2, out=self.bwd)
-        elif self.kind == "head":
-            self.fwd = ops.pack_head9x9(w, out=self.fwd)
-        else:  # tail: forward pack + its input-gradient conv run by the head kernel
-            self.fwd = ops.pack_tail9x9(w, out=self.fwd)
-            self.bwd = ops.pack_head9x9(w.float().flip(2, 3).transpose(0, 1).contiguous(), out=self.bwd)
-
-    @property
-    def bias(self) -> torch.Tensor:
-        return self.b.detach() if self.b is not None else None
-
-
-def _bn_of(m: nn.Module):
-    bn = getattr(m, "bn", None)
-    return bn if isinstance(bn, nn.BatchNorm2d) else None
-
-
-def _generator_convs(gen: nn.Module) -> tuple[TConv, list[list[TConv]], TConv, list[TConv], TConv]:
+def _generator_convs(gen: nn.Module) -> tuple[TrainConv, list[list[TrainConv]], TrainConv, list[TrainConv], TrainConv]:
     """Conv layers of a ResNet / EResNet in execution order (reference module paths)."""
     def t(m: nn.Module, kind="3x3", **kw):
-        conv = m.conv
-        return TConv(conv.weight, conv.bias, conv.in_channels, conv.out_channels, kind, bn=_bn_of(m), **kw)
+        return TrainConv.of(m, kind, **kw)
 
     a = gen.add_rate
     head = t(gen.conv0, "head")
@@ -94,9 +57,10 @@ def _generator_convs(gen: nn.Module) -> tuple[TConv, list[list[TConv]], TConv, l
             # without BN the dgrad of the final conv carries the RDB (x add_rate) scale in the
             # weights (the RRDB-level x add_rate of the third RDB is the epilogue's s2); with BN
             # the scale is applied by the BN backward (gscale) instead
-            fin = _bn_of(rdb.conv)
-            rdbs.append([t(rdb.conv0), t(rdb.conv1), t(rdb.conv2), t(rdb.conv3),
-                         t(rdb.conv, dgrad_scale=(1.0 if fin is not None else a))])
+            fin = t(rdb.conv)
+            if fin.bn is None:
+                fin.dgrad_scale = a
+            rdbs.append([t(rdb.conv0), t(rdb.conv1), t(rdb.conv2), t(rdb.conv3), fin])
     conv1 = t(gen.conv1)
     scalers = [t(s.net[0], sub2=True) for s in gen.scaler]
     tail = t(gen.conv2, "tail")
@@ -156,12 +120,10 @@ class GeneratorTrainPlan:
         self._params, self._goff = [], []
         off = 0
         for c in self.convs:
-            ps = [c.w, c.b] + ([c.bn.weight, c.bn.bias] if c.bn is not None else [])
-            for p in ps:
-                if p is not None:
-                    self._params.append(p)
-                    self._goff.append(off)
-                    off += (p.numel() + 3) // 4 * 4  # 16-byte aligned views
+            for p in c.params():
+                self._params.append(p)
+                self._goff.append(off)
+                off += (p.numel() + 3) // 4 * 4  # 16-byte aligned views
         self._gsize = off
         # RDB input gradients as "gather" convs (no BatchNorm): per RDB, one conv per dense-buffer
         # block — the gradient of block o_t (and of x) is ONE conv over the concatenated output

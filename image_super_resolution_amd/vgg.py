@@ -26,6 +26,7 @@ from torch import nn
 from . import ops
 from ._lib import load as _load_lib
 from .ops import ActBuffer, round_up, TILE_H, TILE_W
+from .train_layers import TrainConv
 
 VGG19_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"]
 
@@ -156,39 +157,25 @@ class VGGPlan:
         self._build()
 
     def _pack(self, vgg):
-        self.packs = []
+        # one TrainConv per conv step, packed once per weights version; the first layer's 3 input
+        # channels fill one padded 16-channel plane (forward) and 32 (dgrad output)
+        self.layers = {}
         for s in self.steps:
-            if s[0] != "conv":
-                continue
-            m = s[1]
-            wt = m.weight.detach().to(self.device, torch.float32)
-            b = m.bias.detach().to(self.device, torch.float32).contiguous()
-            cin = m.in_channels
-            if cin % 16:  # first layer: 3 input channels → one padded plane (forward), 32 (dgrad output)
-                w16 = torch.zeros(wt.shape[0], 16, 3, 3, device=self.device)
-                w16[:, :cin] = wt
-                w32 = torch.zeros(wt.shape[0], 32, 3, 3, device=self.device)
-                w32[:, :cin] = wt
-                fwd, bwd = ops.pack_conv3x3(w16), ops.pack_conv3x3_dgrad(w32)
-            else:
-                fwd, bwd = ops.pack_conv3x3(wt), ops.pack_conv3x3_dgrad(wt)
-            self.packs.append((fwd, bwd, b))
+            if s[0] == "conv":
+                m = s[1]
+                l = self.layers[id(m)] = TrainConv.of(m, "3x3", cin_p=round_up(m.in_channels, 16))
+                l.pack()
         self.version = _weights_version(vgg)
 
     def _build(self):
         F, B = [], []
         lib = self.lib
-        pi = 0
-        conv_meta = []
         for s in self.steps:
             if s[0] == "conv":
                 m, xin, out, relu = s[1], s[2], s[3], s[4]
-                fwd, bwd, b = self.packs[pi]
-                pi += 1
-                cin = xin.c if m.in_channels % 16 else m.in_channels
-                F.append((lib.isr_conv3x3_fwd, ops.conv3x3_desc(xin, cin, fwd, b, m.out_channels, out,
+                l = self.layers[id(m)]
+                F.append((lib.isr_conv3x3_fwd, ops.conv3x3_desc(xin, l.cin_p, l.fwd, l.bias, m.out_channels, out,
                                                                  slope=0.0 if relu else 1.0)))
-                conv_meta.append((m, xin, out, relu, bwd))
             else:
                 xin, out, c = s[1], s[2], s[3]
                 F.append((lib.isr_maxpool2_fwd, ops.pool_desc(xin, out, c)))
@@ -212,7 +199,7 @@ class VGGPlan:
             s = steps[k]
             if s[0] == "conv":
                 m, xin, out, relu = s[1], s[2], s[3], s[4]
-                bwd = next(c[4] for c in conv_meta if c[0] is m)
+                bwd = self.layers[id(m)].bwd
                 g_in_out = gb[id(out)]
                 if xin is self.x:  # first conv: input gradient, 3 of 32 channels meaningful
                     B.append((lib.isr_conv3x3_fwd, ops.conv3x3_desc(g_in_out, m.out_channels, bwd, None, 32,
