@@ -240,6 +240,7 @@ struct TrunkArgs {
     int rec_off;   // words
     int nl;
     int acquire;
+    int keep;      // TRUNK_KEEP_* bits (trunk_keep.h)
 };
 
 
@@ -296,6 +297,11 @@ struct TrunkCtx {
                                  // resource spans ONE plane (a per-(image, plane) base), so the
                                  // buffers themselves may be any size (the 4K still, video batches)
     uint32_t hoff[TK::HPW];       // per-lane halo piece offsets (chunk-invariant)
+    int keep;                    // growth pairs keep their tile in LDS across the phase-2 hand-off
+    uint32_t kbase;              // kept tiles: LDS offset of this lane's epilogue registers of its
+                                 // wave's row 0 inside a slot's halo image (trunk_keep.h)
+    uint32_t ring_src, ring_lds; // kept tiles: this lane's ring unit (threads 0..199), its in-plane
+                                 // source offset and its LDS offset inside a slot's halo image
     int abl;                     // tuning ablation bits (0 in production builds)
 };
 
@@ -322,14 +328,14 @@ __device__ __forceinline__ Src src_of(const TrunkCtx& c, const_rec& rec, int t) 
 // bypass: other workgroups of this launch wrote them).  Returns the vector-memory instructions
 // this wave issued (wave-uniform), for the counted waits.
 __device__ __forceinline__ uint32_t stage_pieces(const uint32_t* hoff, uint32_t pstride, int abl, const Src& s,
-                                                 int chunk, int slot, bool with_bias, int bslot) {
+                                                 int chunk, int slot, bool with_bias, int bslot, bool halo = true) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = wave_id(), lane = threadIdx.x & 63;
     char* dst = smem + slot * TK::SLOT;
     uint32_t n = 0;
     const auto rx = rsrc_n(s.x + (size_t)chunk * pstride, s.xbytes);  // chunk c = plane xp + c
     const uint32_t so = s.h0;
-    if (!(abl & 1)) {
+    if (!(abl & 1) && halo) {  // (kept tiles: weights and bias only, the halo image is written in LDS)
 #pragma unroll
         for (int k = 0; k < TK::HPW; ++k) {
             const int j = wave + TK::WM * k;
@@ -378,7 +384,7 @@ __device__ __forceinline__ uint32_t stage_pieces(const uint32_t* hoff, uint32_t 
 }
 
 __device__ __forceinline__ uint32_t stage_chunk(const TrunkCtx& c, const Src& s, int chunk, int slot, bool with_bias,
-                                                int bslot) {
+                                                int bslot, bool halo = true) {
 #ifdef ISR_TUNING
     // tuning-build check of the ring protocol: the chunk lies inside the layer (chunk < nch: its
     // weights inside the packed table) and the slot inside the ring.  A violation gives the launch
@@ -392,7 +398,38 @@ __device__ __forceinline__ uint32_t stage_chunk(const TrunkCtx& c, const Src& s,
         return 0;
     }
 #endif
-    return stage_pieces(c.hoff, c.pstride, c.abl, s, chunk, slot, with_bias, bslot);
+    return stage_pieces(c.hoff, c.pstride, c.abl, s, chunk, slot, with_bias, bslot, halo);
+}
+
+// Kept tiles: the 9 weight pieces of chunk `chunk` of the 32-cout pack of `rec` (the second layer of
+// a growth pair) into the weight area of ring slot `slot`, where a 32-cout chunk body reads them; the
+// slot's halo image is not touched.  Returns the instructions this wave issued, as stage_pieces.
+__device__ __forceinline__ uint32_t stage_keep_weights(const TrunkCtx& c, const_rec& rec, int chunk, int slot) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int wave = wave_id(), lane = threadIdx.x & 63;
+    const uint32_t wbytes = (uint32_t)(rec_nch(rec) * tk::WPG * 1024), wo = (uint32_t)(chunk * tk::WPG * 1024);
+#ifdef ISR_TUNING
+    // tuning-build check, as in stage_chunk: the chunk's weights lie inside the packed table
+    if (chunk < 0 || wo >= wbytes || slot < 0 || slot >= TK::NST) {
+        if (threadIdx.x == 0) {
+            __hip_atomic_store(c.state + 1, c.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(c.state + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return 0;
+    }
+#endif
+    char* wd = smem + slot * TK::SLOT + TK::HP * 1024;
+    const auto rw = rsrc_n((const char*)(uintptr_t)rec.w, wbytes);
+    uint32_t n = 0;
+#pragma unroll
+    for (int k = 0; k < (tk::WPG + TK::WM - 1) / TK::WM; ++k) {
+        const int j = wave + TK::WM * k;
+        if (j < tk::WPG && !(c.abl & 8)) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, ISR_LDS_PTR(wd + j * 1024), 16, lane * 16, wo + j * 1024, 0, 0);
+            ++n;
+        }
+    }
+    return n;
 }
 
 // The tile that follows the current one in this workgroup's stream.
@@ -421,6 +458,8 @@ struct Stream {
     unsigned pend_v;
     uint32_t pend_mark;   // `issued` right after those stores
     bool dep_next;        // the next tile's neighbourhood has been verified
+    bool kept_next;       // kept tiles: the previous item left this item's chunks 0 and 1 in LDS but for
+                          // their ring (a final conv followed by a growth pair on the same tile)
 };
 
 __device__ __forceinline__ void push_mark(Stream& st) {
@@ -513,11 +552,25 @@ enum : int {
 // chunks once:
 //  * PH 1 (NF = 2, L = the first layer): the shared chunks with the 64-cout chunk bodies, fragment 0
 //    = layer L, fragment 1 = layer L + 1 (weight pieces interleaved from the two 32-cout packs, the
-//    two biases in one bias slot, no fold); its last chunk stages nothing; the growth epilogue on
+//    two biases in one bias slot, no fold); its last chunk stages no halo; the growth epilogue on
 //    fragment 0 alone, pending publish L + 1; fragment 1's accumulators leave in `pacc`;
-//  * PH 2 (NF = 1, L = the second layer): its last two chunks on `pacc`.  The first is always staged
-//    at its own top (drain the stores, publish, wait for the neighbourhood's layer L - 1, stage); the
-//    second stages the next item's chunk 0 as any last chunk does.  Growth epilogue, publish L + 1.
+//  * PH 2 (NF = 1, L = the second layer): its last two chunks on `pacc`.  The first starts at its
+//    own top (drain the stores, publish, wait for the neighbourhood's layer L - 1); the second
+//    stages the next item's chunk 0 as any last chunk does.  Growth epilogue, publish L + 1.
+//  * What phase 2 reads is, but for a ring of 100 halo pixels, what this workgroup has just computed
+//    (trunk_keep.h).  Kept tiles (c.keep, the switch ISR_TRUNK_KEEP, default on): phase 1's last
+//    chunk also stages the weights of phase 2's first chunk into the other slot; phase 1's epilogue
+//    starts with a barrier, stages the weights of phase 2's second chunk into the last chunk's slot
+//    and writes each packed output register to LDS beside its global store (plane 0 = the interior
+//    of phase 2's first chunk, plane 1 = of its second); phase 2, after the neighbourhood wait,
+//    loads only the ring of both chunks (2 loads, 2 LDS writes per thread), waits once, and runs
+//    the two chunks back to back.  The bits in LDS are those the read-back delivered.  With the
+//    switch off phase 1's last chunk stages nothing and phase 2's first chunk is staged whole at
+//    its own top (20 halo pieces, 9 weight pieces), its second inside the first's refill.
+//    The same holds where a final conv is followed by a growth pair on the same tile (a workgroup
+//    that owns one tile, at every RDB boundary): the pair's chunks 0 and 1 are planes 0 and 1 of the
+//    final conv's fragment 0 and are kept in the same way (`keep_nx` below, `st.kept_next`); its
+//    chunks 2 and 3 are staged from HBM as ever.
 // Each accumulator receives the MFMAs of its per-layer tile in the same order (chunk ascending, then
 // dx, dy, row, the same for NF 1 and 2), so the bits are those of the unpaired stream.
 template <int NF, bool MASKED = false, bool H = false, int PH = 0>
@@ -576,6 +629,23 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     st.dep_next = false;
     const int bslot = st.tseq & 3;
     const int first_item = st.item;  // this tile's chunk 0
+    const bool kept = PH != 0 && c.keep != 0;  // growth pairs: the tile stays in LDS across the hand-off
+    // Same-tile layer boundary (c.keep & 2): this is a final conv, and the next item is a growth pair
+    // on the same tile whose chunks 0..3 are this layer's output planes (ntiles <= workgroups: once
+    // per RDB).  That item would be staged at its own top; its chunks 0 and 1 = fragment 0's two planes
+    // are kept as phase 2's are: weights (and bias) of chunk 0 in the last chunk, of chunk 1 in the
+    // epilogue, the interiors from the epilogue's registers.  Chunks 2 and 3 stage as ever.
+    bool keep_nx = false;
+    if constexpr (ROLES && NF == 2 && PH == 0) {
+        const int fm = rec_form(rec);
+        // first_new == 0 says only that the pair's chunk 0 overlaps this layer's 64 output channels (and
+        // that it reads the buffer this layer writes): its first plane must BE output plane 0, or the
+        // pair's chunks 0 and 1 are other planes than fragment 0's (a pair reading from y.coff + 16, + 32
+        // or + 48 is a valid table: it is staged from HBM)
+        keep_nx = (c.keep & 2) && nx_exists && nxt == t && nxL == L + 1 && (fm == EPI_FINAL || fm == EPI_FINAL_R2) &&
+                  rec_first_new(recs[nxL]) == 0 && rec_pair(recs[nxL]) == 1 && rec_xp(recs[nxL]) == rec_yp(rec);
+    }
+    bool both_staged = false;  // this tile's first chunk found its second staged with it (kept tiles)
     trunk_stamp(L, t, c.ntiles, 0);
 
     // per-lane LDS read addresses (slot 0): weights A[n][k] (n = cout), halo rows of this wave
@@ -653,15 +723,44 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                 if (st.staged < st.item) {
                     // not staged (the previous tile's outputs lie in this tile's neighbourhood): drain,
                     // publish, wait, stage
-                    // (pair phase 2 always comes here: phase 1 just wrote this chunk and staged nothing)
+                    // (pair phase 2 always comes here: phase 1 just wrote this chunk and staged no halo)
                     force_publish(c, st);
                     if ((PH == 2 || first_new == 0) && !dep_ok) {
                         wait_deps(t, need);
                         dep_ok = true;
                     }
-                    st.issued += stage_chunk(c, me, ch, slot, PH != 2, bslot);
-                    st.staged = st.item;
-                    st.m0 = st.issued;
+                    bool ring_only = PH == 2 && kept;
+                    if constexpr (PH == 1) {
+                        ring_only = st.kept_next;
+                        st.kept_next = false;
+                    }
+                    if (ring_only) {
+                        both_staged = true;
+                        // kept tile: the interior of both chunks and their weights are in LDS (phase
+                        // 1's epilogue); only the ring, which other workgroups wrote, is fetched: one
+                        // 16-byte sc1 load per chunk by threads 0..199, then the same bits to LDS.
+                        // Both chunks are staged by this: the first chunk issues no refill
+                        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+                        asm volatile("" ::: "memory");  // the loads stay behind the neighbourhood wait
+                        if (threadIdx.x < keep::RING_UNITS && !(c.abl & 1)) {
+                            const char* xa = me.x + (size_t)ch * c.pstride;
+                            const u32x4 ra = __builtin_amdgcn_raw_buffer_load_b128(rsrc_n(xa, c.pstride), c.ring_src, me.h0, TK::HALO_AUX);
+                            const u32x4 rb = __builtin_amdgcn_raw_buffer_load_b128(rsrc_n(xa + c.pstride, c.pstride), c.ring_src, me.h0, TK::HALO_AUX);
+                            *reinterpret_cast<u32x4*>(smem + slot * TK::SLOT + c.ring_lds) = ra;
+                            *reinterpret_cast<u32x4*>(smem + (slot ^ 1) * TK::SLOT + c.ring_lds) = rb;
+                        }
+                        // The loads are compiler-visible: hipcc places their vmcnt wait before the two
+                        // LDS stores, so the counted wait below finds nothing of this chunk in flight;
+                        // the top barrier's lgkmcnt(0) (raw_barrier) is what completes the LDS stores
+                        // before any wave reads the ring.
+                        st.issued += 2;
+                        st.staged = st.item + 1;
+                        st.m0 = st.m1 = st.issued;
+                    } else {
+                        st.issued += stage_chunk(c, me, ch, slot, PH != 2, bslot);
+                        st.staged = st.item;
+                        st.m0 = st.issued;
+                    }
                 }
                 xn += c.pstride;  // the first chunk is staged: the next chunk to stage is the second
                 wo += WSTEP * 1024;
@@ -703,6 +802,7 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                 st.pend_t = -1;
             }
             }
+            if (PH == 2 && ROLE == CR_FIRST) trunk_stamp(L, t, c.ntiles, 1);  // the hand-off is over
             if (PH != 2 && (ROLE == CR_FIRST || (ROLE == CR_GENERAL && ch == 0))) {
                 trunk_stamp(L, t, c.ntiles, 1);
                 // bias → accumulators (register g of lane l: cout (g&3) + 8(g>>2) + 4hh of fragment f)
@@ -770,8 +870,18 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                         st.issued += stage_chunk(c, src_of(c, nrec, nxt), 0, slot ^ 1, true, (bslot + 1) & 3);
                         ++st.staged;
                         st.m1 = st.issued;
+                    } else if (keep_nx) {
+                        // kept across the layer boundary: the next item's chunk-0 weights and its bias
+                        // into the other slot; not counted as staged (the item still starts at its own top)
+                        st.issued += stage_chunk(c, src_of(c, nrec, nxt), 0, slot ^ 1, true, (bslot + 1) & 3, false);
                     }
                 }
+            }
+            if constexpr (PH == 1 && ROLE == CR_LOOP) {
+                // kept tile: the weights of phase 2's first chunk (chunk nch of the second layer's
+                // pack) into the other slot's weight area, idle since this chunk's top barrier; the
+                // halo image of that slot is filled by the epilogue
+                if (last && kept && ring_ok) st.issued += stage_keep_weights(c, recs[L + 1], nch, slot ^ 1);
             }
             if constexpr (ROLE != CR_GENERAL && ROLE != CR_LAST) {
                 if constexpr (ROLE != CR_STEADY) {
@@ -780,7 +890,10 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                         dep_ok = true;
                     }
                 }
-                if (!last && ring_ok) {
+                if (ROLE == CR_FIRST && both_staged) {  // (kept tile: both chunks are in LDS)
+                    xn += c.pstride;
+                    wo += WSTEP * 1024;
+                } else if (!last && ring_ok) {
                     st.issued += stage_own(slot ^ 1);
                     ++st.staged;
                     st.m1 = st.issued;
@@ -925,9 +1038,30 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
     // v_max each, so max(a, a * slope) costs the same 2.5 instructions per value and would still have
     // to be argued for -0 and NaN); the fold layers have slope == 1; u * s2 + r2 is one fused
     // multiply-add in the general body (hipcc contracts it) and an explicit one here.
-    auto epilogue = [&](auto form_tag, auto full_tag) {
+    // KP (pair phase 1 with kept tiles): the tile's two output planes are the halo interiors of phase
+    // 2's two chunks.  One barrier (every wave has finished the last chunk's fragment reads), the
+    // weights of phase 2's second chunk into the last chunk's slot, and beside each global store the
+    // same packed register to LDS: plane 0 into the other slot's halo image (phase 2's first chunk),
+    // plane 1 into the last chunk's.  The row is an immediate offset: no VALU per value.
+    auto epilogue = [&](auto form_tag, auto full_tag, auto keep_tag) {
         constexpr int EF = decltype(form_tag)::value;
         constexpr bool GEN = EF == EPI_GENERAL, FT = decltype(full_tag)::value != 0;
+        constexpr bool KP = decltype(keep_tag)::value != 0;
+        static_assert(!KP || (PH == 1 && EF == EPI_GROWTH) || (PH == 0 && NF == 2 && (EF == EPI_FINAL || EF == EPI_FINAL_R2)),
+                      "kept tiles: pair phase 1, or a final conv before a pair on the same tile");
+        uint32_t kb[2] = {0, 0};
+        if constexpr (KP) {
+            const int cur = (st.item - 1) % NST;  // the last chunk's slot
+            raw_barrier();
+            if constexpr (PH == 1) {
+                st.issued += stage_keep_weights(c, recs[L + 1], nch + 1, cur);
+            } else {  // the next item's chunk 1: the 64-cout weight image of the pair, no bias
+                st.issued += stage_chunk(c, src_of(c, recs[nxL], nxt), 1, cur, false, 0, false);
+                st.kept_next = true;
+            }
+            kb[0] = c.kbase + (uint32_t)((cur ^ 1) * TK::SLOT);
+            kb[1] = c.kbase + (uint32_t)(cur * TK::SLOT);
+        }
         static_assert(GEN || (EF == EPI_GROWTH ? (NF == 1 || PH == 1) && !MASKED : NF == 2 && PH == 0),
                       "form and layer kind");
         const bool use_r2 = GEN ? (has_r2 || masked) : EF == EPI_FINAL_R2;
@@ -1043,28 +1177,38 @@ __device__ __forceinline__ void run_tile(const TrunkCtx& c, Stream& st, const_re
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tq), yr, off, 0, TK::STORE_AUX);
                         ++st.issued;
                     }
+                    if constexpr (KP) {
+                        if (f == 0)  // (a final conv: fragment 1 = planes 2 and 3 are staged from HBM)
+                            *reinterpret_cast<u32x4*>(smem + kb[blk] + r * keep::ROW_STEP) = __builtin_bit_cast(u32x4, tq);
+                    }
                 }
             }
         }
     };
     // one wave-uniform branch per tile into the body of the layer's form (the masked layers: general)
-    auto epilogue_of = [&](auto form_tag) {
-        if (y0 + TK::TH <= c.h && x0 + tk::TW <= c.w) epilogue(form_tag, TIC<1>{});
-        else epilogue(form_tag, TIC<0>{});
+    auto epilogue_of = [&](auto form_tag, auto keep_tag) {
+        if (y0 + TK::TH <= c.h && x0 + tk::TW <= c.w) epilogue(form_tag, TIC<1>{}, keep_tag);
+        else epilogue(form_tag, TIC<0>{}, keep_tag);
     };
     const int form = ROLES ? rec_form(rec) : (int)EPI_GENERAL;
-    if constexpr (PH != 0) {
-        epilogue_of(TIC<EPI_GROWTH>{});  // the prep kernel pairs layers of the growth form only
+    if constexpr (PH == 1) {
+        // the prep kernel pairs layers of the growth form only; one wave-uniform branch on the switch
+        if (kept) epilogue_of(TIC<EPI_GROWTH>{}, TIC<1>{});
+        else epilogue_of(TIC<EPI_GROWTH>{}, TIC<0>{});
+    } else if constexpr (PH == 2) {
+        epilogue_of(TIC<EPI_GROWTH>{}, TIC<0>{});
     } else if constexpr (ROLES && NF == 1) {
-        if (form == EPI_GROWTH) epilogue_of(TIC<EPI_GROWTH>{});
-        else epilogue(TIC<EPI_GENERAL>{}, TIC<0>{});
+        if (form == EPI_GROWTH) epilogue_of(TIC<EPI_GROWTH>{}, TIC<0>{});
+        else epilogue(TIC<EPI_GENERAL>{}, TIC<0>{}, TIC<0>{});
     } else if constexpr (ROLES) {
-        if (form == EPI_FINAL) epilogue_of(TIC<EPI_FINAL>{});
-        else if (form == EPI_FINAL_R2) epilogue_of(TIC<EPI_FINAL_R2>{});
-        else if (form == EPI_FINAL_S2) epilogue_of(TIC<EPI_FINAL_S2>{});
-        else epilogue(TIC<EPI_GENERAL>{}, TIC<0>{});
+        if (keep_nx && form == EPI_FINAL) epilogue_of(TIC<EPI_FINAL>{}, TIC<1>{});
+        else if (keep_nx) epilogue_of(TIC<EPI_FINAL_R2>{}, TIC<1>{});
+        else if (form == EPI_FINAL) epilogue_of(TIC<EPI_FINAL>{}, TIC<0>{});
+        else if (form == EPI_FINAL_R2) epilogue_of(TIC<EPI_FINAL_R2>{}, TIC<0>{});
+        else if (form == EPI_FINAL_S2) epilogue_of(TIC<EPI_FINAL_S2>{}, TIC<0>{});
+        else epilogue(TIC<EPI_GENERAL>{}, TIC<0>{}, TIC<0>{});
     } else {
-        epilogue(TIC<EPI_GENERAL>{}, TIC<0>{});
+        epilogue(TIC<EPI_GENERAL>{}, TIC<0>{}, TIC<0>{});
     }
     trunk_stamp(L, t, c.ntiles, 3);
     st.pend_t = t;
@@ -1109,7 +1253,13 @@ __global__ __launch_bounds__(TK::NT, TK::WPS) void trunk_kernel(TrunkArgs a) {
         const int wave = wave_id(), lane = threadIdx.x & 63;
 #pragma unroll
         for (int k = 0; k < TK::HPW; ++k) c.hoff[k] = halo_piece_off<TK::HQ>(wave + TK::WM * k, lane, c.wp);
+        static_assert(TK::R == keep::ROWS_PER_WAVE && keep::RING_UNITS <= TK::NT, "trunk_keep.h describes this build");
+        c.kbase = keep_epi_lds_off(wave, 0, lane & 31, lane >> 5);
+        const int ru = (int)threadIdx.x < keep::RING_UNITS ? (int)threadIdx.x : 0;
+        c.ring_src = keep_ring_src_off(ru, c.wp);
+        c.ring_lds = keep_ring_lds_off(ru);
     }
+    c.keep = a.keep;
     const int G = gridDim.x, b = (int)blockIdx.x;
     Stream st;
     st.item = 0;
@@ -1121,6 +1271,7 @@ __global__ __launch_bounds__(TK::NT, TK::WPS) void trunk_kernel(TrunkArgs a) {
     st.pend_v = 0;
     st.pend_mark = 0;
     st.dep_next = false;
+    st.kept_next = false;
     if (b < c.ntiles) {
         st.issued += stage_chunk(c, src_of(c, recs[0], b), 0, 0, true, 0);  // layer 0 reads the trunk input only
         st.m0 = st.issued;
@@ -1190,6 +1341,12 @@ static int trunk_launch_k(const isr_chain_desc* cd, hipStream_t s) {
     a.rec_off = rec_off;
     a.nl = cd->nl;
     a.acquire = cd->acquire;
+    // kept tiles: ISR_TRUNK_KEEP = 0 phase 2 of a growth pair stages its chunks whole, 1 (default) the
+    // tile and its weights stay in LDS, across the phase-2 hand-off and across a final conv followed by
+    // a pair on the same tile, 2 across the phase-2 hand-off only (the A/B switch of DESIGN.md section
+    // 5, Kept tiles), read once
+    static const int keep_mode = getenv("ISR_TRUNK_KEEP") ? atoi(getenv("ISR_TRUNK_KEEP")) : 1;
+    a.keep = keep_mode <= 0 ? TRUNK_KEEP_OFF : (keep_mode == 2 ? TRUNK_KEEP_ON : TRUNK_KEEP_ON | TRUNK_KEEP_BOUNDARY);
     hipLaunchKernelGGL((trunk_kernel<H>), dim3(grid), dim3(TK::NT), TK::LDS, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

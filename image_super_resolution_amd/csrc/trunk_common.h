@@ -3,12 +3,13 @@
 #pragma once
 #include "isr_common.h"
 #include "trunk_pairs.h"
+#include "trunk_keep.h"
 
 namespace isr {
 
 namespace tk {
-constexpr int TH = 16;          // tile rows (R x WM of a build)
-constexpr int TW = 32;
+constexpr int TH = keep::TH;    // tile rows (R x WM of a build)
+constexpr int TW = keep::TW;
 constexpr int HR = TH + 2, HC = TW + 2, HQ = HR * HC;  // 18 x 34 halo pixels
 constexpr int HP = (HQ + 31) / 32;                      // 20 halo pieces (1 KB) per chunk
 constexpr int WPG = 9, WPF = 18;                        // weight pieces per chunk: 32 / 64 couts
@@ -126,12 +127,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_n(const void* p, uint32_t
 // 16 lanes of a ds_read_b128 group (columns 8 apart pair up) still hit 16 distinct bank slots.
 template <int HQ>
 __device__ __forceinline__ uint32_t halo_piece_off(int j, int lane, int wp) {
-    const int u = j * 64 + lane;
-    const int q = u >> 1;
-    if (q >= HQ) return 0;  // tail of the last piece: never read
-    const int row = q / tk::HC, col = q - row * tk::HC;
-    const int cc = (u & 1) ^ ((col >> 3) & 1);
-    return (uint32_t)((row * wp + col) * 32 + cc * 16);
+    static_assert(HQ == keep::HQ && tk::HC == keep::HC, "trunk_keep.h describes this halo image");
+    return halo_unit_src(j * 64 + lane, wp);  // 0 on the tail of the last piece: never read
 }
 
 // s_waitcnt vmcnt(n) for a run-time n (0..63): this wave's n youngest vector-memory

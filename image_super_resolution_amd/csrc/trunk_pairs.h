@@ -5,7 +5,10 @@
 // A pair (A = layer L, B = layer L + 1) turns a workgroup's stream for those two layers from
 // layer-major (A on every tile of the workgroup, then B on every tile) into pair-major: for each
 // tile t = b, b + G, ...: phase 1 (A and B on the chunks they share), then phase 2 (B on the two
-// chunks A just wrote).  The blocking waits inside one pair are
+// chunks A just wrote).  Phase 2 always follows phase 1 of the same tile, so the tile's own pixels
+// of those two chunks can stay in LDS (trunk_keep.h) and phase 2 reads only the ring of halo
+// pixels its neighbours wrote: that changes what phase 2 fetches after its wait, not what it waits
+// for.  The blocking waits inside one pair are
 //   P2(a)  -> P1(a')      a' in the 3x3 neighbourhood of a (a itself included): a' <= a + nbx + 1
 //   P1(a') -> P2(a' - G)  the item before it in its workgroup's stream (when a' >= G)
 //   P2(a)  -> P2(n)       a the last tile of workgroup b with a >= b + G, n in the neighbourhood of
