@@ -130,6 +130,11 @@ class IsrResampleDesc(ctypes.Structure):
                 ("hr_norm", c_int32), ("mean", c_float * 3), ("std", c_float * 3)]
 
 
+class IsrBlurDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("src", c_void_p), ("dst", c_void_p),
+                ("ksize", c_void_p), ("median", c_void_p), ("taps", c_void_p)]
+
+
 HLS_PARTIAL_BLOCKS = 32  # ISR_HLS_PARTIAL_BLOCKS
 MT_TENSOR_BYTES = 40 # isr_mt_tensor: 4 pointers + int64
 MT_CHUNK_BYTES = 16   # isr_mt_chunk: int32 t, int32 len, int64 start
@@ -207,6 +212,8 @@ SIGNATURES = {
     "isr_resample_ksize": (c_int32, [c_int32, c_int32, c_int32]),
     "isr_resample_tables": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "isr_resample_u8": (c_int32, [POINTER(IsrResampleDesc), c_void_p]),
+    "isr_blur_taps": (c_int32, [c_int32, c_int32, c_void_p, c_void_p]),
+    "isr_blur_u8": (c_int32, [POINTER(IsrBlurDesc), c_void_p]),
     "isr_last_error": (ctypes.c_char_p, []),
     "isr_version": (c_int32, []),
 }

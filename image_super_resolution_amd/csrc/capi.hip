@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "isr_common.h"
+#include "blur_taps.h"
 #include "resample_tables.h"
 
 namespace isr {
@@ -59,6 +60,7 @@ int jpeg_roundtrip_dispatch(const isr_jpeg_desc* d, void* ws, size_t ws_bytes, h
 int hls_l_moments_dispatch(const isr_hls_moments_desc* d, hipStream_t s);
 int iso_noise_dispatch(const isr_iso_noise_desc* d, hipStream_t s);
 int resample_u8_dispatch(const isr_resample_desc* d, hipStream_t s);
+int blur_u8_dispatch(const isr_blur_desc* d, hipStream_t s);
 }  // namespace isr
 
 static thread_local char g_err[512] = "";
@@ -816,6 +818,41 @@ int isr_resample_u8(const isr_resample_desc* d, isr_stream_t s) {
     rc = isr::resample_u8_dispatch(d, (hipStream_t)s);
     if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "resample_u8: more than 2^31 - 1 workgroups");
     return launched(rc, "resample_u8");
+}
+
+int isr_blur_taps(int kind, int ksize, const double* params, int32_t* taps) {
+    if (!taps) return fail(ISR_ERR_BAD_DESC, "blur_taps: null table");
+    if (!params && (kind == ISR_BLUR_GAUSSIAN || kind == ISR_BLUR_MOTION))
+        return fail(ISR_ERR_BAD_DESC, "blur_taps: kind %d needs params", kind);
+    switch (isr::blur_taps(kind, ksize, params, taps)) {
+        case 0: g_err[0] = 0; return ISR_OK;
+        case 1: return fail(ISR_ERR_UNSUPPORTED, "blur_taps: unknown kind %d (ISR_BLUR_BOX, GAUSSIAN, MOTION = 0..2)", kind);
+        case 2: return fail(ISR_ERR_UNSUPPORTED, "blur_taps: ksize %d is not 3, 5 or 7", ksize);
+        case 3: return fail(ISR_ERR_UNSUPPORTED, "blur_taps: sigma_x, sigma_y and angle must be finite");
+        case 4: return fail(ISR_ERR_UNSUPPORTED, "blur_taps: motion end points (%g, %g) (%g, %g) must be integers in "
+                            "[0, %d]", params[0], params[1], params[2], params[3], ksize - 1);
+        case 5: return fail(ISR_ERR_UNSUPPORTED, "blur_taps: motion end points are equal (%g, %g)", params[0], params[1]);
+        default: return fail(ISR_ERR_UNSUPPORTED, "blur_taps: the centre tap would be negative (kind %d, ksize %d)", kind,
+                             ksize);
+    }
+}
+
+int isr_blur_u8(const isr_blur_desc* d, isr_stream_t s) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "blur_u8: null descriptor");
+    if (!d->src || !d->dst || !d->ksize || !d->median || !d->taps)
+        return fail(ISR_ERR_BAD_DESC, "blur_u8: null src / dst / ksize / median / taps");
+    if (d->n < 1 || d->n > 65535) return fail(ISR_ERR_BAD_DESC, "blur_u8: bad batch n=%d (n in [1, 65535])", d->n);
+    if (d->h < ISR_BLUR_MAX_K || d->w < ISR_BLUR_MAX_K)
+        return fail(ISR_ERR_UNSUPPORTED, "blur_u8: image %dx%d smaller than the %d x %d window", d->h, d->w,
+                    ISR_BLUR_MAX_K, ISR_BLUR_MAX_K);
+    if ((long long)d->n * 3 * d->h * d->w >= (1ll << 31))
+        return fail(ISR_ERR_UNSUPPORTED, "blur_u8: n*3*h*w does not fit 31 bits (n=%d, %dx%d)", d->n, d->h, d->w);
+    if (d->dst == d->src) return fail(ISR_ERR_BAD_DESC, "blur_u8: dst must not be src");
+    if (((uintptr_t)d->ksize | (uintptr_t)d->median | (uintptr_t)d->taps) % 4)
+        return fail(ISR_ERR_BAD_DESC, "blur_u8: ksize, median and taps must be 4-byte aligned");
+    const int rc = isr::blur_u8_dispatch(d, (hipStream_t)s);
+    if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "blur_u8: more than 2^31 - 1 workgroups");
+    return launched(rc, "blur_u8");
 }
 
 }  // extern "C"

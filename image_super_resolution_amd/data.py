@@ -85,16 +85,24 @@ class GPUTransform:
     (isr_resample_u8).  "random" is image_reader's mix (:218-246): per image one of RANDOM_FILTERS
     = (bicubic, bilinear, box, nearest), each with probability 0.25, drawn by exactly one
     torch.randint(0, 4, (n,), generator=self.gen, device=...) per call (self.gen seeded with
-    `seed`) and never read back.  These are HIP kernels: on a CPU device they raise."""
+    `seed`) and never read back.  These are HIP kernels: on a CPU device they raise.
+
+    `degrade` (an LRDegrade, or None) degrades a copy of the crops before the resize, with every
+    lr_filter: hr is made from the clean crops and is bit for bit what it is without `degrade`;
+    lr is the same resize + Normalize of the degraded copy (one more launch of the transform's
+    kernel).  The `random` draw above happens before the degradation's draws and from a generator
+    of its own, so it is the same with and without `degrade`; with every probability 0 lr is
+    unchanged too.  HIP only."""
 
     LR_FILTERS = ("cv2", "nearest", "box", "bilinear", "hamming", "bicubic", "lanczos", "random")
     RANDOM_FILTERS = ("bicubic", "bilinear", "box", "nearest")
 
     def __init__(self, scale: int, hr_norm: bool = False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda",
-                 lr_filter: str = "cv2", seed: int = 0):
+                 lr_filter: str = "cv2", seed: int = 0, degrade: "LRDegrade | None" = None):
         if lr_filter not in self.LR_FILTERS:
             raise ValueError(f"GPUTransform: lr_filter {lr_filter!r} is not one of {', '.join(self.LR_FILTERS)}")
         self.scale, self.hr_norm = scale, hr_norm
+        self.degrade = degrade
         self.lr_filter, self.seed, self.gen = lr_filter, seed, None
         if lr_filter == "random" and torch.device(device).type == "cuda":
             self.gen = torch.Generator(device=device).manual_seed(seed)
@@ -106,6 +114,11 @@ class GPUTransform:
     def __call__(self, crops_u8: torch.Tensor):
         if self.lr_filter != "cv2":
             return self._hip_resample(crops_u8)
+        if self.degrade is not None:
+            # isr_sr_transform makes both outputs: hr is kept from the clean crops, lr from the degraded copy
+            x = crops_u8.to(self.device, non_blocking=True)
+            degraded = self.degrade(x)
+            return self._hip(x)[0], self._hip(degraded)[1]
         if torch.device(self.device).type == "cuda":
             return self._hip(crops_u8)
         # CPU device: the same formulas as torch ops (host-side tests; the GPU path is the kernel)
@@ -158,8 +171,14 @@ class GPUTransform:
         else:
             names, ids = (self.lr_filter,), None
         filters = tuple(degrade.RESAMPLE_FILTERS.index(f) for f in names)
+        kw = dict(hr_norm=self.hr_norm, mean=self.mean_f, std=self.std_f)
+        if self.degrade is not None:
+            _, _, hr = degrade.resample_launch(x, (t // self.scale, t // self.scale), filters, ids, want_hr=True, **kw)
+            _, lr, _ = degrade.resample_launch(self.degrade(x), (t // self.scale, t // self.scale), filters, ids,
+                                               want_lr=True, **kw)
+            return hr, lr
         _, lr, hr = degrade.resample_launch(x, (t // self.scale, t // self.scale), filters, ids, want_lr=True,
-                                            want_hr=True, hr_norm=self.hr_norm, mean=self.mean_f, std=self.std_f)
+                                            want_hr=True, **kw)
         return hr, lr
 
 
@@ -238,6 +257,167 @@ class NoisyTransform:
             q = torch.randint(int(lo), int(hi) + 1, (n,), device=self.device, generator=g, dtype=torch.int32)
             u8 = degrade.jpeg_roundtrip(u8, q * on.to(torch.int32))
         return u8
+
+
+class LRDegrade:
+    """The blind-SR degradation of the HR crops that the LR image is then resized from: the stages
+    the reference lists, commented out, ahead of SR_dataset.transform_lr's Resize
+    (utils/datasets.py:291-305), in its order, each applied per image with its own probability,
+    exchanging uint8 [n, 3, t, t] images:
+
+    1. ISONoise (`iso_p`; color_shift / intensity uniform in `iso_color_shift` / `iso_intensity`);
+    2. ImageCompression (`jpeg_p`; a JPEG round trip at an integer quality uniform in the inclusive
+       `jpeg_quality`; the crop side must then be a multiple of 16);
+    3. blur (`blur_p`): ONE draw among `blur_kinds` ("box", "gaussian", "motion", "median", uniform)
+       with k uniform in `blur_ksizes` (default 3, 5, 7) — not the reference's four independent
+       stages Blur, GaussianBlur, MotionBlur and MedianBlur, whose probabilities `blind` sums.
+       Gaussian: sigma_x, sigma_y uniform in [0.2, 3.0], angle in [0, pi); motion: a line between
+       two points of the k x k grid drawn as albumentations' MotionBlur draws them;
+    4. GaussNoise (`gauss_p`; variance uniform in `var_limit` on the 0-255 scale, per channel, the
+       result clipped and truncated to uint8).
+
+    The input is not written to.  All four are HIP kernels or device tensor ops (degrade.iso_noise,
+    jpeg_roundtrip, blur_u8): a CPU tensor raises.  Nothing is read back from the device.
+
+    Draws.  Stages 1, 2 and 4 draw from a device generator seeded with `seed`, as NoisyTransform
+    does, and only when their probability is > 0: ISONoise rand(n), uniform(n) color shift,
+    uniform(n) intensity, then degrade.iso_noise's poisson(n, t, t) and randn(n, t, t); JPEG rand(n),
+    randint(n); GaussNoise uniform(n, 1, 1, 1), rand(n, 1, 1, 1), randn(n, 3, t, t).  The blur stage
+    draws on the HOST from a CPU generator seeded with `seed`, when blur_p > 0, exactly five float64 /
+    int64 tensors per call, whatever is applied:
+        a = torch.rand(n)            apply where a < blur_p
+        b = torch.randint(0, len(blur_kinds), (n,))   the kind, an index into blur_kinds
+        c = torch.randint(0, len(blur_ksizes), (n,))  k = blur_ksizes[c]
+        g = torch.rand(n, 3)         sigma_x = 0.2 + 2.8 g0, sigma_y = 0.2 + 2.8 g1, angle = pi g2
+        m = torch.rand(n, 4)         x1 = floor(k m0), x2 = floor(k m1), y1 = floor(k m2), and
+                                     y2 = floor(k m3) if x1 != x2 else (y1 + 1 + floor((k - 1) m3)) mod k
+    (`blur_params` is that, as plain Python).  The [n, 49] tap table is built by libisr's host code
+    (degrade.blur_taps) and goes up in one non-blocking copy from pinned memory.  One motion draw has
+    no table: a six-pixel line (k = 7) that misses the centre pixel rounds to taps summing to 65538,
+    which isr_blur_taps refuses; that image is left unblurred."""
+
+    BLUR_KINDS = ("box", "gaussian", "motion", "median")
+
+    def __init__(self, iso_p: float = 0.0, jpeg_p: float = 0.0, jpeg_quality=(45, 75), blur_p: float = 0.0,
+                 blur_kinds=BLUR_KINDS, gauss_p: float = 0.0, var_limit=(10.0, 50.0), iso_color_shift=(0.01, 0.05),
+                 iso_intensity=(0.1, 0.5), seed: int = 0, device="cuda", blur_ksizes=(3, 5, 7)):
+        blur_kinds, blur_ksizes = tuple(blur_kinds), tuple(int(k) for k in blur_ksizes)
+        if not blur_ksizes or any(k not in (3, 5, 7) for k in blur_ksizes):
+            raise ValueError(f"LRDegrade: blur_ksizes {blur_ksizes!r} must be a non-empty choice of 3, 5 and 7")
+        if not blur_kinds or any(k not in self.BLUR_KINDS for k in blur_kinds):
+            raise ValueError(f"LRDegrade: blur_kinds {blur_kinds!r} must be a non-empty subset of {self.BLUR_KINDS}")
+        lo, hi = jpeg_quality
+        if int(lo) != lo or int(hi) != hi or not 1 <= lo <= hi <= 100:
+            raise ValueError(f"LRDegrade: jpeg quality range must be integers with 1 <= lower <= upper <= 100, "
+                             f"got {jpeg_quality}")
+        for name, p in (("iso_p", iso_p), ("jpeg_p", jpeg_p), ("blur_p", blur_p), ("gauss_p", gauss_p)):
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"LRDegrade: {name} = {p} is not a probability")
+        self.iso_p, self.jpeg_p, self.blur_p, self.gauss_p = float(iso_p), float(jpeg_p), float(blur_p), float(gauss_p)
+        self.jpeg_quality, self.blur_kinds, self.var_limit = (int(lo), int(hi)), blur_kinds, var_limit
+        self.blur_ksizes = blur_ksizes
+        self.iso_color_shift, self.iso_intensity = iso_color_shift, iso_intensity
+        self.seed, self.device = seed, device
+        self.gen = torch.Generator(device=device).manual_seed(seed)
+        self.host_gen = torch.Generator(device="cpu").manual_seed(seed)
+
+    PRESETS = {
+        # the blur stage alone
+        "blur": dict(blur_p=0.5),
+        # the probabilities of the reference's commented list (ISONoise 0.05, ImageCompression 0.1 at quality
+        # 45..75, Blur + GaussianBlur + MotionBlur + MedianBlur 0.05 + 0.1 + 0.1 + 0.05, GaussNoise 0.1)
+        "blind": dict(iso_p=0.05, jpeg_p=0.1, jpeg_quality=(45, 75), blur_p=0.3, gauss_p=0.1),
+    }
+
+    @classmethod
+    def preset(cls, name: str, **kw):
+        """`train.py --lr_degrade`'s chains: "blur" or "blind" (PRESETS)."""
+        if name not in cls.PRESETS:
+            raise ValueError(f"LRDegrade: unknown preset {name!r}; one of {', '.join(cls.PRESETS)}")
+        return cls(**cls.PRESETS[name], **kw)
+
+    @staticmethod
+    def blur_params(n: int, blur_p: float, blur_kinds, gen: torch.Generator, blur_ksizes=(3, 5, 7)) -> list[dict]:
+        """The blur stage's host draws of one call of n images from the CPU generator `gen` (the
+        class docstring's five tensors), decoded: per image a dict with `apply`, `kind`, `ksize`
+        and, for gaussian and motion, `params` (degrade.blur_taps' keywords)."""
+        import math
+        a = torch.rand(n, generator=gen, dtype=torch.float64).tolist()
+        b = torch.randint(0, len(blur_kinds), (n,), generator=gen).tolist()
+        c = torch.randint(0, len(blur_ksizes), (n,), generator=gen).tolist()
+        g = torch.rand(n, 3, generator=gen, dtype=torch.float64).tolist()
+        m = torch.rand(n, 4, generator=gen, dtype=torch.float64).tolist()
+        out = []
+        for i in range(n):
+            k, kind = blur_ksizes[c[i]], blur_kinds[b[i]]
+            rec = dict(apply=a[i] < blur_p, kind=kind, ksize=k, params={})
+            if kind == "gaussian":
+                rec["params"] = dict(sigma_x=0.2 + 2.8 * g[i][0], sigma_y=0.2 + 2.8 * g[i][1], angle=math.pi * g[i][2])
+            elif kind == "motion":
+                x1, x2, y1 = (min(int(k * v), k - 1) for v in m[i][:3])
+                y2 = min(int(k * m[i][3]), k - 1) if x1 != x2 else (y1 + 1 + min(int((k - 1) * m[i][3]), k - 2)) % k
+                rec["params"] = dict(x1=x1, y1=y1, x2=x2, y2=y2)
+            out.append(rec)
+        return out
+
+    def _check(self, u8: torch.Tensor) -> None:
+        if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[1] != 3:
+            raise ValueError(f"LRDegrade expects uint8 [n, 3, t, t] crops, got {getattr(u8, 'dtype', type(u8))} "
+                             f"{tuple(getattr(u8, 'shape', ()))}")
+        h, w = u8.shape[-2:]
+        if self.jpeg_p > 0 and (h % 16 or w % 16):
+            raise ValueError(f"LRDegrade: jpeg_p = {self.jpeg_p} needs whole 16 x 16 MCUs, but the crop is {h}x{w}: "
+                             "choose a crop side that is a multiple of 16, or jpeg_p = 0")
+        if not u8.is_cuda or torch.device(self.device).type != "cuda":
+            raise RuntimeError("LRDegrade: the degradations are HIP kernels (MI355X only); got a tensor on "
+                               f"{u8.device} for device {self.device!r} (there is no host fallback)")
+
+    def __call__(self, crops_u8: torch.Tensor) -> torch.Tensor:
+        from . import degrade
+        self._check(crops_u8)
+        u8 = crops_u8.contiguous()
+        n, dev, g = u8.shape[0], u8.device, self.gen
+        if self.iso_p > 0:
+            on = torch.rand(n, device=dev, generator=g) < self.iso_p
+            cs = torch.empty(n, device=dev).uniform_(*self.iso_color_shift, generator=g)
+            it = torch.empty(n, device=dev).uniform_(*self.iso_intensity, generator=g)
+            u8 = degrade.iso_noise(u8, cs, it, g, apply=on)
+        if self.jpeg_p > 0:
+            on = torch.rand(n, device=dev, generator=g) < self.jpeg_p
+            lo, hi = self.jpeg_quality
+            q = torch.randint(lo, hi + 1, (n,), device=dev, generator=g, dtype=torch.int32)
+            u8 = degrade.jpeg_roundtrip(u8, q * on.to(torch.int32))
+        if self.blur_p > 0:
+            u8 = self._blur(u8)
+        if self.gauss_p > 0:
+            var = torch.empty(n, 1, 1, 1, device=dev).uniform_(*self.var_limit, generator=g)
+            on = (torch.rand(n, 1, 1, 1, device=dev, generator=g) < self.gauss_p).float()
+            noise = torch.randn(u8.shape, device=dev, generator=g) * var.sqrt() * on
+            u8 = (u8.float() + noise).clamp_(0, 255).to(torch.uint8)
+        return u8
+
+    def _blur(self, u8: torch.Tensor) -> torch.Tensor:
+        """The blur stage: host draws, host-built tables, one isr_blur_u8 launch."""
+        from . import _lib, degrade
+        n = u8.shape[0]
+        # one pinned block per call: [n][49 taps, ksize, median]; ksize 0 copies the image through
+        host = torch.zeros((n, 51), dtype=torch.int32).pin_memory()
+        for i, rec in enumerate(self.blur_params(n, self.blur_p, self.blur_kinds, self.host_gen,
+                                                    self.blur_ksizes)):
+            if not rec["apply"]:
+                continue
+            host[i, 49] = rec["ksize"]
+            if rec["kind"] == "median":
+                host[i, 50] = 1
+            else:
+                try:
+                    taps = degrade.blur_taps(rec["kind"], rec["ksize"], **rec["params"])
+                except _lib.IsrError:  # the refused motion line (class docstring): the image stays as it is
+                    host[i, 49] = 0
+                    continue
+                host[i, :49] = torch.from_numpy(taps.reshape(49))
+        dev = host.to(u8.device, non_blocking=True)
+        return degrade.blur_u8(u8, dev[:, 49], dev[:, 50], dev[:, :49].reshape(n, 7, 7))
 
 
 NATURAL_ALPHA = 1.4  # amplitude spectrum 1/f^alpha: x4 bicubic PSNR ~27.7 dB, the regime of COCO crops

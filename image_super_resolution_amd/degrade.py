@@ -8,6 +8,12 @@ tensors, and a quality of 0 / an apply flag of 0 copies the image through.
 bit: the LR models of the reference's Random_low_rs and image_reader (utils/datasets.py:23-32,
 :218-246).  Its coefficient tables are made on the host by libisr (`resample_tables`, plain C++).
 
+`blur_u8` (with `filter_u8`, `median_u8`) is the blur family the reference lists, commented out,
+ahead of SR_dataset's Resize (utils/datasets.py:291-305: Blur, GaussianBlur, MotionBlur,
+MedianBlur): an integer k x k correlation with 16-bit fixed-point taps (`blur_taps`, made on the host
+by libisr) or the exact k x k median, k in {3, 5, 7} per image; data.LRDegrade chains it with the
+two above and GaussNoise for the blind-SR LR model.
+
 GPU-only, like the rest of the product path: a CPU tensor raises.
 """
 from __future__ import annotations
@@ -204,3 +210,88 @@ def resample_u8(u8: torch.Tensor, size, filter="bicubic") -> torch.Tensor:
     with torch.cuda.device(x.device):
         ids = _per_image(ids, n, torch.int32, x.device, "resample_u8: filter")
     return resample_launch(x, size, tuple(range(len(RESAMPLE_FILTERS))), ids, want_u8=True)[0]
+
+
+BLUR_KINDS = ("box", "gaussian", "motion")  # index = ISR_BLUR_*
+BLUR_MAX_K = 7
+_BLUR_PARAMS = {"box": (), "gaussian": ("sigma_x", "sigma_y", "angle"), "motion": ("x1", "y1", "x2", "y2")}
+
+
+def blur_taps(kind, ksize: int, **params) -> np.ndarray:
+    """A 7 x 7 tap table from libisr's host code (isr_blur_taps, no GPU): numpy int32, 16
+    fractional bits, the ksize x ksize window (3, 5 or 7) in the centre, summing to exactly 65536.
+    `kind`: "box"; "gaussian" with sigma_x, sigma_y (<= 0 or absent: cv2's rule for the ksize)
+    and angle in radians (default 0); "motion" with the integer end points x1, y1, x2, y2 of a
+    Bresenham line inside the window."""
+    if isinstance(kind, str):
+        if kind not in BLUR_KINDS:
+            raise ValueError(f"blur_taps: unknown kind {kind!r}; one of {', '.join(BLUR_KINDS)}")
+        kind = BLUR_KINDS.index(kind)
+    name = BLUR_KINDS[kind] if 0 <= int(kind) < len(BLUR_KINDS) else None
+    names = _BLUR_PARAMS.get(name, ())
+    extra = sorted(set(params) - set(names))
+    if extra:
+        raise ValueError(f"blur_taps: {name} takes no parameter {', '.join(extra)}")
+    if name == "motion" and len(params) != 4:
+        raise ValueError("blur_taps: motion needs x1, y1, x2 and y2")
+    vals = (ctypes.c_double * 4)(*[float(params.get(n, 0.0)) for n in names])
+    taps = np.zeros((BLUR_MAX_K, BLUR_MAX_K), dtype=np.int32)
+    _lib.check(_lib.load().isr_blur_taps(int(kind), int(ksize), ctypes.cast(vals, ctypes.c_void_p), taps.ctypes.data),
+               "isr_blur_taps")
+    return taps
+
+
+def _blur_tables(taps, n: int, device) -> torch.Tensor:
+    """int32 [n, 49] on `device` from a [7, 7] table for the whole batch or [n, 7, 7] per image."""
+    t = torch.from_numpy(np.ascontiguousarray(taps)) if isinstance(taps, np.ndarray) else taps
+    if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.dtype == torch.bool:
+        raise ValueError("blur: taps must be an integer array or tensor")
+    if tuple(t.shape) == (BLUR_MAX_K, BLUR_MAX_K):
+        t = t.unsqueeze(0).expand(n, -1, -1)
+    if tuple(t.shape) != (n, BLUR_MAX_K, BLUR_MAX_K):
+        raise ValueError(f"blur: taps must be [7, 7] or [{n}, 7, 7], got {tuple(t.shape)}")
+    return t.to(device=device, dtype=torch.int32, non_blocking=True).reshape(n, BLUR_MAX_K * BLUR_MAX_K).contiguous()
+
+
+def _blur_ints(v, n: int, device, what: str) -> torch.Tensor:
+    if isinstance(v, torch.Tensor):
+        if v.is_floating_point():
+            raise ValueError(f"{what} must be an integer tensor, got {v.dtype}")
+    elif not isinstance(v, (int, bool, np.integer)):
+        v = torch.tensor([int(k) for k in v], dtype=torch.int32)
+    return _per_image(v, n, torch.int32, device, what)
+
+
+def blur_u8(u8: torch.Tensor, ksize, median, taps) -> torch.Tensor:
+    """One isr_blur_u8 launch on uint8 [n, 3, h, w] (h, w >= 7): per image, `ksize` 3, 5 or 7 (any
+    other value copies the image through), `median` non-zero for the exact k x k median (border
+    replicated), else the correlation with the centre k x k of the image's 7 x 7 `taps` (16
+    fractional bits, border reflect-101, rounded half up and clipped).  ksize and median: an int or
+    an int sequence / tensor [n]; taps: int32 [7, 7] or [n, 7, 7]; numpy, host or device tensors
+    (device tensors stay on the device; nothing is read back)."""
+    x = _checked(u8, "blur_u8")
+    n, _, h, w = x.shape
+    with torch.cuda.device(x.device):
+        k = _blur_ints(ksize, n, x.device, "blur_u8: ksize")
+        m = _blur_ints(median, n, x.device, "blur_u8: median")
+        t = _blur_tables(taps, n, x.device)
+        out = torch.empty_like(x)
+        d = _lib.IsrBlurDesc(n, h, w, x.data_ptr(), out.data_ptr(), k.data_ptr(), m.data_ptr(), t.data_ptr())
+        _lib.check(_lib.load().isr_blur_u8(ctypes.byref(d), _stream()), "isr_blur_u8")
+    return out
+
+
+def filter_u8(u8: torch.Tensor, taps, ksize=None) -> torch.Tensor:
+    """The integer correlation of every image with `taps` (blur_taps' tables, or any int32 table with
+    sum |tap| <= 2^23, negative taps included).  `ksize` (default 7) bounds the window that is read;
+    zero taps inside it cost time, not accuracy."""
+    return blur_u8(u8, BLUR_MAX_K if ksize is None else ksize, 0, taps)
+
+
+_zero_taps = np.zeros((BLUR_MAX_K, BLUR_MAX_K), dtype=np.int32)
+
+
+def median_u8(u8: torch.Tensor, ksize) -> torch.Tensor:
+    """The exact ksize x ksize median of every image, border replicated (cv2.medianBlur, Pillow's
+    MedianFilter).  `ksize`: 3, 5 or 7, an int or an int tensor [n]; 0 copies that image through."""
+    return blur_u8(u8, ksize, 1, _zero_taps)

@@ -678,6 +678,69 @@ typedef struct isr_resample_desc {
 } isr_resample_desc;
 int isr_resample_u8(const isr_resample_desc* d, isr_stream_t s);
 
+/* ---- Blur degradations (LR synthesis) -----------------------------------------
+ * The blur family of the reference's commented LR stages (utils/datasets.py:291-305: Blur,
+ * GaussianBlur, MotionBlur, MedianBlur) on 8-bit images, in integer arithmetic from host-made
+ * tables.
+ *
+ * isr_blur_taps (host, plain C++, no GPU) fills a 7 x 7 table of fixed-point taps with
+ * ISR_BLUR_BITS = 16 fractional bits.  ksize must be 3, 5 or 7; the k x k window sits in the centre
+ * of the table, the rest is zero.  The fp64 weights w (below), one rounding per operation, are
+ * summed in row-major order and divided by the sum; tap = floor(w * 65536 + 0.5); then the centre
+ * tap receives 65536 - (sum of the taps), so every table sums to exactly 65536 and has no negative
+ * tap.  A parameter set whose centre tap would become negative is refused.
+ *   ISR_BLUR_BOX       no params (NULL allowed): w = 1 on the k x k window.
+ *   ISR_BLUR_GAUSSIAN  params = {sigma_x, sigma_y, angle_rad}.  With (dx, dy) the tap's offset from the
+ *                      centre, u = (dx cos a + dy sin a) / sigma_x, v = (dy cos a - dx sin a) / sigma_y,
+ *                      w = exp(-0.5 (u u + v v)).  A sigma <= 0 stands for cv2's rule
+ *                      0.3 ((k - 1) 0.5 - 1) + 0.8 (albumentations' GaussianBlur at sigma_limit = 0).
+ *   ISR_BLUR_MOTION    params = {x1, y1, x2, y2}: integer end points in [0, k - 1]^2 (x = column, y = row
+ *                      of the window), not equal (albumentations' MotionBlur).  w = 1 on the pixels of
+ *                      the line, which is this algorithm and nothing else (parity with cv2.line is not
+ *                      pinned):
+ *                          dx = |x2 - x1|, sx = x1 < x2 ? 1 : -1, dy = -|y2 - y1|, sy = y1 < y2 ? 1 : -1,
+ *                          err = dx + dy, (x, y) = (x1, y1);
+ *                          loop: mark (x, y); stop if (x, y) == (x2, y2); e2 = 2 err;
+ *                                if e2 >= dy: err += dy, x += sx;   if e2 <= dx: err += dx, y += sy.
+ *                      A line that misses the centre pixel leaves it the rounding residual alone.
+ * Refused with ISR_ERR_UNSUPPORTED: an unknown kind, another ksize, a sigma or angle that is not
+ * finite, end points that are not integers of the grid or are equal, a negative centre tap;
+ * ISR_ERR_BAD_DESC: a null table, null params for a kind that has some. */
+#define ISR_BLUR_MAX_K 7
+#define ISR_BLUR_BITS 16
+#define ISR_BLUR_BOX 0
+#define ISR_BLUR_GAUSSIAN 1
+#define ISR_BLUR_MOTION 2
+int isr_blur_taps(int kind, int ksize, const double* params, int32_t* taps /* [49] */);
+
+/* isr_blur_u8: src uint8 planar [n][3][h][w] -> dst of the same shape, per image i:
+ *   ksize[i] not in {3, 5, 7}   dst = src (a copy-through; median[i] and the table are ignored);
+ *   median[i] == 0              acc = sum over the k x k window of tap * pixel (int32, formed in
+ *                               unsigned arithmetic: a table too large wraps),
+ *                               dst = clip((acc + 32768) >> 16, 0, 255), the shift arithmetic (floor);
+ *                               border reflect-101 (-1 -> 1, h -> h - 2: cv2's default for blur,
+ *                               GaussianBlur and filter2D).  The window is the centre k x k of image
+ *                               i's table taps[i][7][7] (row-major, row = vertical offset): taps
+ *                               outside it are not read.  Any table with sum |tap| <= 2^23 is exact
+ *                               (a sharpening kernel with negative taps, say); the clip makes it safe;
+ *   median[i] != 0              the exact median of the k x k window, border replicated (cv2's
+ *                               medianBlur, Pillow's MedianFilter): the smallest v with at least
+ *                               (k k + 1) / 2 window pixels <= v.
+ * ksize, median and taps are DEVICE arrays.  Source indices are clamped to the image after the border
+ * rule, so no value in them can make the kernel read or write outside the images.  One launch on `s`:
+ * no workspace, no allocation, no synchronisation.  h, w >= 7; n in [1, 65535]; n*3*h*w < 2^31; dst
+ * must not be src; ksize, median and taps 4-byte aligned (src and dst: any alignment; 4-byte aligned
+ * with w % 4 == 0 takes the dword loads and stores). */
+typedef struct isr_blur_desc {
+    int32_t n, h, w;
+    const uint8_t* src;
+    uint8_t* dst;
+    const int32_t* ksize;  /* device, [n]: 3, 5 or 7; any other value copies that image through */
+    const int32_t* median; /* device, [n]: non-zero = median of the k x k window */
+    const int32_t* taps;   /* device, [n][49]: a linear image's table */
+} isr_blur_desc;
+int isr_blur_u8(const isr_blur_desc* d, isr_stream_t s);
+
 const char* isr_last_error(void);
 int isr_version(void);
 

@@ -17,7 +17,10 @@ entry in the checkpoint and a copy of it as <checkpoint stem>.best.pt when PSNR-
 these flags nothing changes.  `--lr_filter` chooses how the LR image is made from the HR crop, for
 training and validation: cv2 (the default, SR_dataset's INTER_LINEAR without antialiasing), one of
 Pillow's antialiased filters (bicubic, ...: Image.resize bit for bit, one HIP launch) or random
-(image_reader's per-sample mix); the val_*.jsonl line records it.  Every mode trains on the HIP path: ResNet (train-mode BatchNorm kernels)
+(image_reader's per-sample mix); the val_*.jsonl line records it.  `--lr_degrade blur|blind` degrades
+a copy of the HR crop before that resize, for training only (data.LRDegrade: blur alone, or the
+reference's commented ISONoise / JPEG / blur / GaussNoise chain); validation stays on the undegraded LR.
+Every mode trains on the HIP path: ResNet (train-mode BatchNorm kernels)
 and EResNet (`--enchant`) in `--resnet` pixel-loss mode and in SRGAN mode (VGG
 perceptual + adversarial, discriminator on libisr), and the Denoise model
 (`--train_denoise`).
@@ -124,6 +127,12 @@ def val_batches(opt, device) -> list:
 def lr_filter_of(opt) -> str:
     """--lr_filter of a parsed command line; "cv2" (SR_dataset's resize) when the flag was not given."""
     return getattr(opt, "lr_filter", "cv2")
+
+
+def lr_degrade_of(opt, device, seed: int):
+    """The data.LRDegrade of --lr_degrade for GPUTransform; None when the flag was not given."""
+    name = getattr(opt, "lr_degrade", None)
+    return None if name is None else data.LRDegrade.preset(name, device=device, seed=seed)
 
 
 class _Validation:
@@ -328,7 +337,8 @@ def main(opt):
         model, ema, compute_loss, optimizer, schedule, start = setup_resnet(opt, device, group, iters, res_ck)
         print(f"Train: ResNet {opt.epochs} epochs, {sum(p.numel() for p in model.parameters()):,} parameters")
         transform = data.GPUTransform(opt.scale, hr_norm=False, mean=mean, std=std, device=device,
-                                      lr_filter=lr_filter_of(opt), seed=opt.seed + rank)
+                                      lr_filter=lr_filter_of(opt), seed=opt.seed + rank,
+                                      degrade=lr_degrade_of(opt, device, opt.seed * 13 + rank))
         val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, res_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train(model, ema, batches, transform, compute_loss, optimizer, scaler_gen, schedule,
@@ -349,7 +359,8 @@ def main(opt):
         print(f"Train: {opt.epochs} epochs, gen {sum(p.numel() for p in gen_net.parameters()):,} parameters, "
               f"dis {sum(p.numel() for p in dis_net.parameters()):,} parameters")
         transform = data.GPUTransform(opt.scale, hr_norm=True, mean=mean, std=std, device=device,
-                                      lr_filter=lr_filter_of(opt), seed=opt.seed + rank)
+                                      lr_filter=lr_filter_of(opt), seed=opt.seed + rank,
+                                      degrade=lr_degrade_of(opt, device, opt.seed * 13 + rank))
         val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, gen_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train_srgan(gen_net, ema, dis_net, batches, transform, compute_loss, optimizer_g,
@@ -425,11 +436,17 @@ def parse(argv=None):
                    "(the reference SR_dataset's INTER_LINEAR without antialiasing), one of Pillow's antialiased "
                    "resampling filters (bit-exact Image.resize; bicubic is the usual SR benchmark degradation), or "
                    "random (the reference image_reader's per-sample mix of bicubic / bilinear / box / nearest)")
+    p.add_argument("--lr_degrade", default=argparse.SUPPRESS, choices=tuple(data.LRDegrade.PRESETS),
+                   help="degrade a copy of the HR crop before the LR resize (training only; validation keeps the "
+                   "undegraded LR): blur (box / Gaussian / motion / median blur, k in 3, 5, 7, p = 0.5) or blind (the "
+                   "reference's commented chain: ISONoise 0.05, JPEG 0.1 at quality 45..75, blur 0.3, GaussNoise 0.1)")
     opt = p.parse_args(argv)
     if opt.val_every < 1:
         p.error("--val_every must be at least 1")
     if lr_filter_of(opt) != "cv2" and opt.train_denoise:
         p.error("--lr_filter chooses the super-resolution LR model; --train_denoise has no LR image")
+    if hasattr(opt, "lr_degrade") and opt.train_denoise:
+        p.error("--lr_degrade degrades the super-resolution LR image; --train_denoise has no LR image")
     if not opt.data and Path("train_images.json").is_file():
         opt.data = "train_images.json"
     if opt.steps == 0:
