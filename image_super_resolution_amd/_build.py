@@ -12,6 +12,7 @@ ISR_LIB=<path>.  The production libisr.so never contains them.
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -35,6 +36,36 @@ WAIT_CHECKED = ("wgrad3x3.hip", "conv9x9.hip")
 
 def sources() -> list[Path]:
     return sorted(CSRC.glob("*.hip"))
+
+
+def device_asm(src, defines=(), root: Path = ROOT, remarks: bool = False):
+    """The gfx950 device assembly hipcc makes of one .hip with the library's FLAGS (`defines`: further
+    options such as -DISR_TUNING); with remarks, (assembly, the compiler's kernel-resource remarks).  For
+    another checkout, `root` re-roots the public include path; csrc headers are taken from beside `src`."""
+    src = Path(src)
+    swap = {str(ROOT / "include"): str(Path(root) / "include"), str(CSRC): str(src.parent)}
+    cmd = [HIPCC, *(swap.get(f, f) for f in FLAGS), *defines, "--cuda-device-only", "-S", str(src), "-o", "-"]
+    r = subprocess.run(cmd + (["-Rpass-analysis=kernel-resource-usage"] if remarks else []), capture_output=True,
+                       text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc -S failed on {src}:\n{r.stderr}")
+    return (r.stdout, r.stderr) if remarks else r.stdout
+
+
+def kernel_resources(src, defines=(), remarks: str | None = None) -> dict[str, dict[str, str]]:
+    """{mangled kernel name: {remark field: value}} from hipcc's kernel-resource remarks on one .hip
+    (fields such as "VGPRs", "VGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]").
+    `remarks`: those of a device_asm(..., remarks=True) already made, to save the compile."""
+    out, cur = {}, None
+    for line in (device_asm(src, defines, remarks=True)[1] if remarks is None else remarks).splitlines():
+        m = re.search(r"remark: (.*) \[-Rpass-analysis", line)
+        if m:
+            key, _, val = m.group(1).strip().partition(":")
+            if key == "Function Name":
+                cur = out.setdefault(val.strip(), {})
+            elif cur is not None:
+                cur[key.strip()] = val.strip()
+    return out
 
 
 def _needs_build() -> bool:
@@ -80,12 +111,11 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
             import check_lds_waits
         finally:
             sys.path.pop(0)
-        asm = check_lds_waits.device_asm(src, ["-DISR_TUNING"] if tuning else [])
-        errs = check_lds_waits.check_asm(asm, src.name)
+        errs = check_lds_waits.check_asm(device_asm(src, ["-DISR_TUNING"] if tuning else []), src.name)
         if tuning and errs:
             # the tuning library also carries A/B forms of the weight-gradient kernels that never ship
             # (measured slower): a hazard there is reported, and fatal only in a production kernel
-            prod = set(check_lds_waits.kernels(check_lds_waits.device_asm(src, []))[0])
+            prod = set(check_lds_waits.kernels(device_asm(src))[0])
             for e in errs:
                 if e.split(":", 1)[0] not in prod:
                     print(f"[build] tuning-only kernel, not fatal: {e}", file=sys.stderr)

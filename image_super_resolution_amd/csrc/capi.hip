@@ -2,6 +2,7 @@
 // Validation happens here so that a bad descriptor never reaches a kernel:
 // every kernel indexes its tiles without bounds checks.
 #include <stdarg.h>
+#include <initializer_list>
 #include <stdio.h>
 #include <string.h>
 
@@ -81,6 +82,32 @@ static int launched(int rc, const char* what) {
     }
     g_err[0] = 0;
     return ISR_OK;
+}
+
+// A dispatch that takes a workspace answers -3 when it is smaller than the size query's figure.
+static int workspace_too_small(const char* what, size_t ws_bytes, size_t need) {
+    return fail(ISR_ERR_BAD_DESC, "%s: workspace of %zu bytes is smaller than %zu", what, ws_bytes, need);
+}
+
+// The batch rule of the uint8 [n, 3, h, w] entry points: n in [1, 65535] (a grid extent), h and w at least
+// min_side (1, or a kernel's window: then a smaller image is unsupported, not malformed) and, with fits31,
+// n*3*h*w below 2^31 (such kernels index the batch with an int).
+static int batch_ok(const char* what, int n, int h, int w, bool fits31, int min_side = 1) {
+    if (n < 1 || n > 65535) return fail(ISR_ERR_BAD_DESC, "%s: bad batch n=%d (n in [1, 65535])", what, n);
+    if (h < min_side || w < min_side)
+        return fail(min_side > 1 ? ISR_ERR_UNSUPPORTED : ISR_ERR_BAD_DESC, "%s: image %dx%d smaller than %d x %d", what,
+                    h, w, min_side, min_side);
+    if (fits31 && (long long)n * 3 * h * w >= (1ll << 31))
+        return fail(ISR_ERR_UNSUPPORTED, "%s: n*3*h*w = %lld does not fit 31 bits (n=%d, %dx%d)", what,
+                    (long long)n * 3 * h * w, n, h, w);
+    return ISR_OK;
+}
+
+// Every pointer of the list a multiple of `align` (a null one passes: presence is checked apart).
+static bool aligned(uintptr_t align, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if ((uintptr_t)p % align) return false;
+    return true;
 }
 
 // A view must hold rows [-halo, ha + halo) and cols [-halo, wa + halo) of the
@@ -455,8 +482,7 @@ static int wgrad3x3_parts(const isr_wgrad_desc* d, int32_t variant, void* worksp
                                                    variant, variant >= 1 && variant <= 15 ? " (tuning form: build with "
                                                    "-DISR_TUNING)" : "");
     rc = isr::wgrad3x3_dispatch(d, variant, workspace, ws_bytes, (hipStream_t)s, parts);
-    if (rc == -3) return fail(ISR_ERR_BAD_DESC, "wgrad3x3: workspace of %zu bytes is smaller than %zu", ws_bytes,
-                              isr::wgrad3x3_workspace_bytes(d, variant));
+    if (rc == -3) return workspace_too_small("wgrad3x3", ws_bytes, isr::wgrad3x3_workspace_bytes(d, variant));
     if (rc == -2)
         return fail(ISR_ERR_UNSUPPORTED, "wgrad3x3: variant %d needs ha %% stage rows == 0 and cout / cin multiples "
                     "of its tile", variant);
@@ -497,8 +523,8 @@ int isr_wgrad3x3_group_variant(const isr_wgrad_desc* descs, int32_t n, int32_t v
     if (!workspace) return fail(ISR_ERR_BAD_DESC, "wgrad3x3 group: null workspace");
     if (variant != 0 && variant != 1) return fail(ISR_ERR_UNSUPPORTED, "wgrad3x3 group: no variant %d", variant);
     rc = isr::wgrad3x3_group_dispatch(descs, n, workspace, ws_bytes, (hipStream_t)s, variant);
-    if (rc == -3) return fail(ISR_ERR_BAD_DESC, "wgrad3x3 group: workspace of %zu bytes is smaller than %zu", ws_bytes,
-                              isr::wgrad3x3_group_workspace_bytes(descs, n, variant));
+    if (rc == -3)
+        return workspace_too_small("wgrad3x3 group", ws_bytes, isr::wgrad3x3_group_workspace_bytes(descs, n, variant));
     if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "wgrad3x3 group: a member's cout / cin / ha does not fit the tile");
     return launched(rc, "wgrad3x3 group");
 }
@@ -541,7 +567,7 @@ int isr_wgrad9x9(const isr_wgrad9_desc* d, void* workspace, size_t ws_bytes, isr
     if (rc != ISR_OK) return rc;
     if (!workspace) return fail(ISR_ERR_BAD_DESC, "wgrad9x9: null workspace");
     rc = isr::wgrad9x9_dispatch(d, workspace, ws_bytes, (hipStream_t)s);
-    if (rc == -3) return fail(ISR_ERR_BAD_DESC, "wgrad9x9: workspace too small");
+    if (rc == -3) return workspace_too_small("wgrad9x9", ws_bytes, isr::wgrad9x9_workspace_bytes(d));
     return launched(rc, "wgrad9x9");
 }
 
@@ -676,8 +702,7 @@ int isr_bn_bwd_apply(const isr_bn_desc* d, isr_stream_t s) { return bn_run(d, 4,
 static int metrics_validate(const isr_metrics_desc* d, bool need_ptrs) {
     if (!d) return fail(ISR_ERR_BAD_DESC, "image_metrics: null descriptor");
     if (need_ptrs && (!d->a || !d->b || !d->out)) return fail(ISR_ERR_BAD_DESC, "image_metrics: null a / b / out");
-    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
-        return fail(ISR_ERR_BAD_DESC, "image_metrics: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
+    if (int rc = batch_ok("image_metrics", d->n, d->h, d->w, false)) return rc;
     if (d->border < 0) return fail(ISR_ERR_BAD_DESC, "image_metrics: negative border %d", d->border);
     const long long hc = (long long)d->h - 2ll * d->border, wc = (long long)d->w - 2ll * d->border;
     if (hc < 11 || wc < 11)
@@ -696,8 +721,7 @@ int isr_image_metrics(const isr_metrics_desc* d, void* workspace, size_t ws_byte
     if (rc != ISR_OK) return rc;
     if (!workspace) return fail(ISR_ERR_BAD_DESC, "image_metrics: null workspace");
     rc = isr::image_metrics_dispatch(d, workspace, ws_bytes, (hipStream_t)s);
-    if (rc == -3) return fail(ISR_ERR_BAD_DESC, "image_metrics: workspace of %zu bytes is smaller than %zu", ws_bytes,
-                              isr::image_metrics_workspace_bytes(d));
+    if (rc == -3) return workspace_too_small("image_metrics", ws_bytes, isr::image_metrics_workspace_bytes(d));
     return launched(rc, "image_metrics");
 }
 
@@ -707,15 +731,11 @@ static int jpeg_validate(const isr_jpeg_desc* d, bool need_ptrs) {
     if (!d) return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: null descriptor");
     if (need_ptrs && (!d->src || !d->dst || !d->quality))
         return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: null src / dst / quality");
-    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
-        return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
+    if (int rc = batch_ok("jpeg_roundtrip", d->n, d->h, d->w, true)) return rc;
     if (d->h % 16 || d->w % 16)
         return fail(ISR_ERR_UNSUPPORTED, "jpeg_roundtrip: %dx%d is not whole 4:2:0 MCUs: h and w must be multiples "
                     "of 16", d->h, d->w);
-    if ((long long)d->n * 3 * d->h * d->w >= (1ll << 31))
-        return fail(ISR_ERR_UNSUPPORTED, "jpeg_roundtrip: n*3*h*w = %lld does not fit 31 bits",
-                    (long long)d->n * 3 * d->h * d->w);
-    if (need_ptrs && (((uintptr_t)d->src | (uintptr_t)d->dst) % 16 || (uintptr_t)d->quality % 4))
+    if (need_ptrs && !(aligned(16, {d->src, d->dst}) && aligned(4, {d->quality})))
         return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: src and dst must be 16-byte aligned, quality 4-byte aligned");
     return ISR_OK;
 }
@@ -728,20 +748,18 @@ size_t isr_jpeg_roundtrip_workspace_bytes(const isr_jpeg_desc* d) {
 int isr_jpeg_roundtrip(const isr_jpeg_desc* d, void* workspace, size_t ws_bytes, isr_stream_t s) {
     int rc = jpeg_validate(d, true);
     if (rc != ISR_OK) return rc;
-    if (!workspace || (uintptr_t)workspace % 16)
+    if (!workspace || !aligned(16, {workspace}))
         return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: null or not 16-byte aligned workspace");
     rc = isr::jpeg_roundtrip_dispatch(d, workspace, ws_bytes, (hipStream_t)s);
-    if (rc == -3) return fail(ISR_ERR_BAD_DESC, "jpeg_roundtrip: workspace of %zu bytes is smaller than %zu", ws_bytes,
-                              isr::jpeg_roundtrip_workspace_bytes(d));
+    if (rc == -3) return workspace_too_small("jpeg_roundtrip", ws_bytes, isr::jpeg_roundtrip_workspace_bytes(d));
     return launched(rc, "jpeg_roundtrip");
 }
 
 int isr_hls_l_moments(const isr_hls_moments_desc* d, isr_stream_t s) {
     if (!d || !d->src || !d->out || !d->partials)
         return fail(ISR_ERR_BAD_DESC, "hls_l_moments: null descriptor / src / out / partials");
-    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
-        return fail(ISR_ERR_BAD_DESC, "hls_l_moments: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
-    if ((uintptr_t)d->out % 8 || (uintptr_t)d->partials % 8)
+    if (int rc = batch_ok("hls_l_moments", d->n, d->h, d->w, false)) return rc;
+    if (!aligned(8, {d->out, d->partials}))
         return fail(ISR_ERR_BAD_DESC, "hls_l_moments: out and partials must be 8-byte aligned");
     return launched(isr::hls_l_moments_dispatch(d, (hipStream_t)s), "hls_l_moments");
 }
@@ -749,9 +767,8 @@ int isr_hls_l_moments(const isr_hls_moments_desc* d, isr_stream_t s) {
 int isr_iso_noise(const isr_iso_noise_desc* d, isr_stream_t s) {
     if (!d || !d->src || !d->dst || !d->lum_noise || !d->hue_noise || !d->apply)
         return fail(ISR_ERR_BAD_DESC, "iso_noise: null descriptor / src / dst / lum_noise / hue_noise / apply");
-    if (d->n < 1 || d->h < 1 || d->w < 1 || d->n > 65535)
-        return fail(ISR_ERR_BAD_DESC, "iso_noise: bad problem n=%d h=%d w=%d (n in [1, 65535])", d->n, d->h, d->w);
-    if (((uintptr_t)d->lum_noise | (uintptr_t)d->hue_noise | (uintptr_t)d->apply) % 4)
+    if (int rc = batch_ok("iso_noise", d->n, d->h, d->w, false)) return rc;
+    if (!aligned(4, {d->lum_noise, d->hue_noise, d->apply}))
         return fail(ISR_ERR_BAD_DESC, "iso_noise: lum_noise, hue_noise and apply must be 4-byte aligned");
     const long long hw = (long long)d->h * d->w;
     if ((hw + 255) / 256 >= (1ll << 31))
@@ -803,13 +820,11 @@ int isr_resample_u8(const isr_resample_desc* d, isr_stream_t s) {
     if (d->hr_f32 && (d->in_h % d->out_h || d->in_w % d->out_w))
         return fail(ISR_ERR_UNSUPPORTED, "resample_u8: hr_f32 needs an integer ratio on both axes, got %dx%d -> %dx%d",
                     d->in_h, d->in_w, d->out_h, d->out_w);
-    if ((long long)d->n * 3 * d->in_h * d->in_w >= (1ll << 31) || (long long)d->n * 3 * d->out_h * d->out_w >= (1ll << 31))
-        return fail(ISR_ERR_UNSUPPORTED, "resample_u8: n*3*h*w does not fit 31 bits (n=%d, %dx%d -> %dx%d)", d->n,
-                    d->in_h, d->in_w, d->out_h, d->out_w);
+    if ((rc = batch_ok("resample_u8", d->n, d->in_h, d->in_w, true))) return rc;
+    if ((rc = batch_ok("resample_u8", d->n, d->out_h, d->out_w, true))) return rc;
     if (d->dst_u8 == d->src) return fail(ISR_ERR_BAD_DESC, "resample_u8: dst_u8 must not be src");
-    if (((uintptr_t)d->src | (uintptr_t)d->dst_u8 | (uintptr_t)d->bounds_x | (uintptr_t)d->coeffs_x |
-         (uintptr_t)d->bounds_y | (uintptr_t)d->coeffs_y | (uintptr_t)d->filter_id) % 4 ||
-        ((uintptr_t)d->lr_f32 | (uintptr_t)d->hr_f32) % 16)
+    if (!(aligned(4, {d->src, d->dst_u8, d->bounds_x, d->coeffs_x, d->bounds_y, d->coeffs_y, d->filter_id}) &&
+          aligned(16, {d->lr_f32, d->hr_f32})))
         return fail(ISR_ERR_BAD_DESC, "resample_u8: src, dst_u8, tables and filter_id must be 4-byte aligned, lr_f32 "
                     "and hr_f32 16-byte aligned");
     if (d->lr_f32 || (d->hr_f32 && d->hr_norm))
@@ -841,14 +856,9 @@ int isr_blur_u8(const isr_blur_desc* d, isr_stream_t s) {
     if (!d) return fail(ISR_ERR_BAD_DESC, "blur_u8: null descriptor");
     if (!d->src || !d->dst || !d->ksize || !d->median || !d->taps)
         return fail(ISR_ERR_BAD_DESC, "blur_u8: null src / dst / ksize / median / taps");
-    if (d->n < 1 || d->n > 65535) return fail(ISR_ERR_BAD_DESC, "blur_u8: bad batch n=%d (n in [1, 65535])", d->n);
-    if (d->h < ISR_BLUR_MAX_K || d->w < ISR_BLUR_MAX_K)
-        return fail(ISR_ERR_UNSUPPORTED, "blur_u8: image %dx%d smaller than the %d x %d window", d->h, d->w,
-                    ISR_BLUR_MAX_K, ISR_BLUR_MAX_K);
-    if ((long long)d->n * 3 * d->h * d->w >= (1ll << 31))
-        return fail(ISR_ERR_UNSUPPORTED, "blur_u8: n*3*h*w does not fit 31 bits (n=%d, %dx%d)", d->n, d->h, d->w);
+    if (int rc = batch_ok("blur_u8", d->n, d->h, d->w, true, ISR_BLUR_MAX_K)) return rc;  // the k x k window
     if (d->dst == d->src) return fail(ISR_ERR_BAD_DESC, "blur_u8: dst must not be src");
-    if (((uintptr_t)d->ksize | (uintptr_t)d->median | (uintptr_t)d->taps) % 4)
+    if (!aligned(4, {d->ksize, d->median, d->taps}))
         return fail(ISR_ERR_BAD_DESC, "blur_u8: ksize, median and taps must be 4-byte aligned");
     const int rc = isr::blur_u8_dispatch(d, (hipStream_t)s);
     if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "blur_u8: more than 2^31 - 1 workgroups");

@@ -27,12 +27,15 @@ from . import _lib
 from .ops import _stream
 
 
-def _checked(u8: torch.Tensor, what: str) -> torch.Tensor:
-    if not isinstance(u8, torch.Tensor) or not u8.is_cuda:
+def _checked(u8: torch.Tensor, what: str, on_device: bool = True) -> torch.Tensor:
+    """The uint8 [n, 3, h, w] batch check of everything here and of data.py's transforms (`what` names the
+    caller); with on_device the batch must also be on a HIP device.  Returns it contiguous."""
+    if on_device and not (isinstance(u8, torch.Tensor) and u8.is_cuda):
         raise RuntimeError(f"{what}: the input must be a HIP device tensor (the degradations run on the MI355X HIP "
                            f"path only; got {getattr(u8, 'device', type(u8))})")
-    if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[1] != 3:
-        raise ValueError(f"{what}: expected uint8 [n, 3, h, w], got {u8.dtype} {tuple(u8.shape)}")
+    if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[1] != 3:
+        raise ValueError(f"{what}: expected uint8 [n, 3, h, w], got {getattr(u8, 'dtype', type(u8))} "
+                         f"{tuple(getattr(u8, 'shape', ()))}")
     return u8.contiguous()
 
 
@@ -44,20 +47,36 @@ def _per_image(v, n: int, dtype, device, what: str) -> torch.Tensor:
     return torch.full((n,), v, dtype=dtype, device=device)
 
 
+def _per_image_ints(v, n: int, device, what: str, host_range=None) -> torch.Tensor:
+    """Device int32 [n] from an int (Python or numpy), an int sequence or an integer tensor [n]; float and
+    bool tensors are refused.  A device tensor stays on the device and is never read back, so `host_range`
+    = (lo, hi) bounds only what is on the host.  n None: the checks alone (jpeg_roundtrip's come first)."""
+    bad = False
+    if isinstance(v, torch.Tensor):
+        if v.is_floating_point() or v.dtype == torch.bool:
+            raise ValueError(f"{what} must be an integer tensor, got {v.dtype}")
+    elif np.ndim(v):
+        v = torch.tensor([int(k) for k in v], dtype=torch.int32)
+    else:
+        bad = int(v) != v
+        v = v if bad else int(v)
+    if host_range is not None and not bad:
+        if not isinstance(v, torch.Tensor):
+            bad = not host_range[0] <= v <= host_range[1]
+        elif not v.is_cuda and v.numel():
+            bad = not host_range[0] <= int(v.min()) <= int(v.max()) <= host_range[1]
+    if bad:
+        raise ValueError(f"{what} must be an integer" + ("" if host_range is None else " in {}..{}".format(*host_range)) +
+                         f", got {v}")
+    return v if n is None else _per_image(v, n, torch.int32, device, what)
+
+
 def jpeg_roundtrip(u8: torch.Tensor, quality) -> torch.Tensor:
     """The decoded pixels of a baseline 4:2:0 JPEG of every image (libjpeg's arithmetic with an
     fp32 DCT; no entropy coding happens).  `quality`: an int, or an int tensor [n] (kept on the
     device); 1..100, and 0 returns that image unchanged.  h and w must be multiples of 16."""
-    if isinstance(quality, torch.Tensor):
-        if quality.is_floating_point() or quality.dtype == torch.bool:
-            raise ValueError(f"jpeg_roundtrip: quality must be an integer tensor, got {quality.dtype}")
-        if not quality.is_cuda:  # a host tensor is checked here; a device one is clamped by the kernel
-            if quality.numel() and (int(quality.min()) < 0 or int(quality.max()) > 100):
-                raise ValueError("jpeg_roundtrip: quality must be in 0..100 (0 = copy through)")
-    else:
-        if int(quality) != quality or not 0 <= int(quality) <= 100:
-            raise ValueError(f"jpeg_roundtrip: quality must be an integer in 0..100 (0 = copy through), got {quality}")
-        quality = int(quality)
+    # a host quality is checked here; a device one is clamped by the kernel
+    quality = _per_image_ints(quality, None, None, "jpeg_roundtrip: quality", host_range=(0, 100))
     x = _checked(u8, "jpeg_roundtrip")
     n, _, h, w = x.shape
     lib = _lib.load()
@@ -204,11 +223,8 @@ def resample_u8(u8: torch.Tensor, size, filter="bicubic") -> torch.Tensor:
     n = x.shape[0]
     if isinstance(filter, (str, int)):
         return resample_launch(x, size, (_filter_index(filter),), None, want_u8=True)[0]
-    if isinstance(filter, torch.Tensor) and (filter.is_floating_point() or filter.dtype == torch.bool):
-        raise ValueError(f"resample_u8: filter ids must be an integer tensor, got {filter.dtype}")
-    ids = filter if isinstance(filter, torch.Tensor) else torch.tensor([int(f) for f in filter], dtype=torch.int32)
     with torch.cuda.device(x.device):
-        ids = _per_image(ids, n, torch.int32, x.device, "resample_u8: filter")
+        ids = _per_image_ints(filter, n, x.device, "resample_u8: filter ids")
     return resample_launch(x, size, tuple(range(len(RESAMPLE_FILTERS))), ids, want_u8=True)[0]
 
 
@@ -253,15 +269,6 @@ def _blur_tables(taps, n: int, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.int32, non_blocking=True).reshape(n, BLUR_MAX_K * BLUR_MAX_K).contiguous()
 
 
-def _blur_ints(v, n: int, device, what: str) -> torch.Tensor:
-    if isinstance(v, torch.Tensor):
-        if v.is_floating_point():
-            raise ValueError(f"{what} must be an integer tensor, got {v.dtype}")
-    elif not isinstance(v, (int, bool, np.integer)):
-        v = torch.tensor([int(k) for k in v], dtype=torch.int32)
-    return _per_image(v, n, torch.int32, device, what)
-
-
 def blur_u8(u8: torch.Tensor, ksize, median, taps) -> torch.Tensor:
     """One isr_blur_u8 launch on uint8 [n, 3, h, w] (h, w >= 7): per image, `ksize` 3, 5 or 7 (any
     other value copies the image through), `median` non-zero for the exact k x k median (border
@@ -272,8 +279,8 @@ def blur_u8(u8: torch.Tensor, ksize, median, taps) -> torch.Tensor:
     x = _checked(u8, "blur_u8")
     n, _, h, w = x.shape
     with torch.cuda.device(x.device):
-        k = _blur_ints(ksize, n, x.device, "blur_u8: ksize")
-        m = _blur_ints(median, n, x.device, "blur_u8: median")
+        k = _per_image_ints(ksize, n, x.device, "blur_u8: ksize")
+        m = _per_image_ints(median, n, x.device, "blur_u8: median")
         t = _blur_tables(taps, n, x.device)
         out = torch.empty_like(x)
         d = _lib.IsrBlurDesc(n, h, w, x.data_ptr(), out.data_ptr(), k.data_ptr(), m.data_ptr(), t.data_ptr())

@@ -6,7 +6,6 @@ undefined-behaviour sanitizers, the C ABI's layout and refusals, LRDegrade's ref
 device and its host draws, and train.py's --lr_degrade flag."""
 import ctypes
 import math
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,6 +15,7 @@ from PIL import Image, ImageFilter
 from scipy import ndimage
 
 import blur_ref as B
+import host_program
 from conftest import ROOT
 from image_super_resolution_amd import _lib, data, degrade
 
@@ -121,27 +121,15 @@ def test_builder_refusals():
         degrade.blur_taps("motion", 3, x1=0, y1=0)
 
 
-GXX = shutil.which("g++")
-
-
-@pytest.mark.skipif(GXX is None, reason="needs g++")
+@pytest.mark.skipif(host_program.GXX is None, reason="needs g++")
 def test_tap_builder_standalone_under_sanitizers(tmp_path):
     """csrc/blur_taps.h in a program of its own (tests/blur_taps_main.cpp), plain and with
-    -fsanitize=address,undefined: both run clean over every kind, ksize and refusal, print the same
-    lines, and those are the tables libisr hands to Python (sum and position-weighted sum)."""
-    out = {}
-    for tag, extra in (("plain", []), ("san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                               "-fno-omit-frame-pointer"])):
-        exe = tmp_path / f"taps_{tag}"
-        cmd = [GXX, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", *extra, "-I",
-               str(ROOT / "image_super_resolution_amd" / "csrc"), str(ROOT / "tests" / "blur_taps_main.cpp"), "-o", str(exe)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and not r.stderr.strip(), r.stdout[-1000:] + r.stderr[-4000:]
-        out[tag] = r.stdout
-    assert out["plain"] == out["san"], "the sanitizer build computes something else"
-    rows = [line.split() for line in out["plain"].splitlines()]
+    -fsanitize=address,undefined (tests/host_program.py): both run clean over every kind, ksize and
+    refusal, print the same lines, and those are the tables libisr hands to Python (sum and
+    position-weighted sum)."""
+    (out,) = host_program.run_plain_and_sanitized(ROOT / "tests" / "blur_taps_main.cpp", tmp_path,
+                                                  extra_flags=("-ffp-contract=off",))
+    rows = [line.split() for line in out.splitlines()]
     assert {int(r[6]) for r in rows} == {0, 1, 2, 3, 4, 5, 6}  # made, and refused for each of the six reasons
     weights = np.arange(1, 50, dtype=np.int64)
     checked = 0
@@ -229,24 +217,6 @@ def test_desc_layout_matches_c(tmp_path):
         assert getattr(_lib.IsrBlurDesc, name).offset == int(c[name][0]), name
     assert [int(v) for v in c["consts"]] == [B.MAX_K, B.BITS, 0, 1, 2]
     assert degrade.BLUR_KINDS == B.KINDS and degrade.BLUR_MAX_K == B.MAX_K
-
-
-def test_blur_u8_refuses_before_any_launch():
-    lib = _lib.load()
-    p = 0x10000  # never dereferenced: every case is refused first
-
-    def desc(**kw):
-        f = dict(n=2, h=16, w=16, src=p, dst=2 * p, ksize=3 * p, median=4 * p, taps=5 * p)
-        f.update(kw)
-        return _lib.IsrBlurDesc(*(f[name] for name, _ in _lib.IsrBlurDesc._fields_))
-
-    assert lib.isr_blur_u8(None, None) == -1 and b"null descriptor" in lib.isr_last_error()
-    for kw in (dict(h=6), dict(w=6), dict(h=0)):
-        assert lib.isr_blur_u8(ctypes.byref(desc(**kw)), None) == -2 and b"smaller than" in lib.isr_last_error()
-    for kw in (dict(n=0), dict(n=-1), dict(n=65536), dict(src=None), dict(dst=None), dict(ksize=None),
-               dict(median=None), dict(taps=None), dict(dst=p), dict(taps=5 * p + 2)):
-        assert lib.isr_blur_u8(ctypes.byref(desc(**kw)), None) == -1 and lib.isr_last_error(), kw
-    assert lib.isr_blur_u8(ctypes.byref(desc(n=4, h=16384, w=16384)), None) == -2 and b"31 bits" in lib.isr_last_error()
 
 
 def test_cpu_tensors_are_refused():

@@ -2,8 +2,6 @@
 compile for gfx950 without scratch (the median's window and the taps stay in registers), without
 VGPR or SGPR spills, and with no more than 80 KiB of LDS per block (two blocks per CU)."""
 import os
-import re
-import subprocess
 
 import pytest
 
@@ -12,27 +10,9 @@ from image_super_resolution_amd import _build
 LDS_LIMIT = 80 * 1024
 
 
-def _resources():
-    cmd = [_build.HIPCC, *_build.FLAGS, "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-           str(_build.CSRC / "blur.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: (.*) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        key, _, val = m.group(1).strip().partition(":")
-        if key == "Function Name":
-            cur = out.setdefault(val.strip(), {})
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return out
-
-
 @pytest.mark.skipif(not os.path.exists(_build.HIPCC), reason="needs hipcc")
 def test_blur_kernel_resources():
-    res = {k: v for k, v in _resources().items() if "blur_u8_kernel" in k}
+    res = {k: v for k, v in _build.kernel_resources(_build.CSRC / "blur.hip").items() if "blur_u8_kernel" in k}
     assert len(res) == 1, f"blur_u8_kernel not found: {sorted(res)}"
     (r,) = res.values()
     print(f"blur_u8_kernel: VGPRs {r['VGPRs']}, TotalSGPRs {r['TotalSGPRs']}, LDS {r['LDS Size [bytes/block]']} B, "

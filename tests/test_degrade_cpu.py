@@ -1,7 +1,7 @@
 """Host-side checks of the training-data degradations (no GPU): the numpy restatement of the JPEG
 round trip (tests/degrade_ref.py, the reference of tests/test_gpu_degrade.py) against PIL's
-libjpeg, the quantisation tables, the C-ABI validation of the three entry points, and
-NoisyTransform's unchanged default path."""
+libjpeg, the quantisation tables, the C ABI's symbols and struct layouts (its refusals are rows of
+tests/test_capi_refusals.py), and NoisyTransform's unchanged default path."""
 import ctypes
 import io
 
@@ -70,35 +70,6 @@ def test_symbols_exported_and_bound(built_lib):
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES
         assert getattr(built_lib, name) is not None
-
-
-def test_validation_without_a_launch(built_lib):
-    lib = built_lib
-    dummy = 1 << 20  # aligned, never dereferenced
-    assert lib.isr_jpeg_roundtrip(None, None, 0, None) == -1
-    assert lib.isr_jpeg_roundtrip_workspace_bytes(None) == 0
-    assert lib.isr_hls_l_moments(None, None) == -1
-    assert lib.isr_iso_noise(None, None) == -1
-    d = _lib.IsrJpegDesc(1, 24, 32, dummy, dummy, dummy)
-    assert lib.isr_jpeg_roundtrip(ctypes.byref(d), dummy, 1 << 20, None) == -2
-    assert b"16" in lib.isr_last_error()
-    assert lib.isr_jpeg_roundtrip_workspace_bytes(ctypes.byref(d)) == 0
-    d = _lib.IsrJpegDesc(2, 32, 48, dummy, dummy, dummy)
-    assert lib.isr_jpeg_roundtrip_workspace_bytes(ctypes.byref(d)) == 2 * 32 * 48 * 3 // 2
-    assert lib.isr_jpeg_roundtrip(ctypes.byref(d), dummy, 16, None) == -1  # workspace too small
-    assert b"workspace" in lib.isr_last_error()
-    d = _lib.IsrJpegDesc(0, 32, 48, dummy, dummy, dummy)
-    assert lib.isr_jpeg_roundtrip(ctypes.byref(d), dummy, 1 << 20, None) == -1
-    d = _lib.IsrJpegDesc(1, 32, 48, dummy, 0, dummy)
-    assert lib.isr_jpeg_roundtrip(ctypes.byref(d), dummy, 1 << 20, None) == -1
-    m = _lib.IsrHlsMomentsDesc(1, 0, 8, dummy, dummy, dummy)
-    assert lib.isr_hls_l_moments(ctypes.byref(m), None) == -1
-    m = _lib.IsrHlsMomentsDesc(1, 8, 8, dummy, dummy, 0)
-    assert lib.isr_hls_l_moments(ctypes.byref(m), None) == -1
-    i = _lib.IsrIsoNoiseDesc(1, 8, 8, dummy, dummy, dummy, 0, dummy)
-    assert lib.isr_iso_noise(ctypes.byref(i), None) == -1
-    i = _lib.IsrIsoNoiseDesc(1, 8, -1, dummy, dummy, dummy, dummy, dummy)
-    assert lib.isr_iso_noise(ctypes.byref(i), None) == -1
 
 
 def test_struct_layouts_match_c(tmp_path):

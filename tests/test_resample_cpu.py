@@ -5,9 +5,7 @@ builder as a stand-alone program under the address and undefined-behaviour sanit
 
 Zero differing values is the condition throughout: Pillow's 8-bit resampler is integer arithmetic
 on coefficients rounded from doubles, and the restatement follows its order of operations."""
-import ctypes
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +13,7 @@ import pytest
 import torch
 from PIL import Image
 
+import host_program
 import resample_ref as R
 from conftest import ROOT
 from image_super_resolution_amd import _lib, data, degrade
@@ -123,28 +122,6 @@ def test_table_refusals(lib):
         degrade.resample_tables("bicubic", 90, 10)
 
 
-def _desc(**kw):
-    """A descriptor that passes every check (its pointers are never followed: each call below is
-    refused before anything is launched)."""
-    p = 0x10000
-    f = dict(n=2, in_h=48, in_w=48, out_h=12, out_w=12, nf=1, ksize_x=17, ksize_y=17, src=p, bounds_x=p, coeffs_x=p,
-             bounds_y=p, coeffs_y=p, filter_id=None, dst_u8=2 * p, lr_f32=None, hr_f32=None, hr_norm=0,
-             mean=(ctypes.c_float * 3)(0.5, 0.5, 0.5), std=(ctypes.c_float * 3)(0.25, 0.25, 0.25))
-    f.update(kw)
-    return _lib.IsrResampleDesc(**f)
-
-
-def test_kernel_descriptor_refusals(lib):
-    assert lib.isr_resample_u8(None, None) == -1 and _message(lib)
-    for what, d in {"integer ratio": _desc(out_h=13, hr_f32=0x30000), "ratio": _desc(in_w=109),
-                    "sizes": _desc(out_w=0), "ksize": _desc(ksize_x=50)}.items():
-        assert lib.isr_resample_u8(ctypes.byref(d), None) == UNSUPPORTED, what
-        assert what in _message(lib), (what, _message(lib))
-    for d in (_desc(dst_u8=None), _desc(src=None), _desc(nf=0), _desc(n=0), _desc(dst_u8=0x10000),
-              _desc(lr_f32=0x30004), _desc(coeffs_y=None)):
-        assert lib.isr_resample_u8(ctypes.byref(d), None) == -1 and _message(lib)
-
-
 def test_cpu_device_keeps_cv2_and_refuses_the_rest():
     from oracle import ref_cpu
     crops = torch.randint(0, 256, (2, 3, 48, 48), generator=torch.Generator().manual_seed(3), dtype=torch.uint8)
@@ -164,30 +141,15 @@ def test_cpu_device_keeps_cv2_and_refuses_the_rest():
     np.testing.assert_allclose(lr.numpy(), ref, rtol=0, atol=2e-6)
 
 
-GXX = shutil.which("g++")
-
-
-@pytest.mark.skipif(GXX is None, reason="needs g++")
+@pytest.mark.skipif(host_program.GXX is None, reason="needs g++")
 def test_table_builder_standalone_under_sanitizers(lib, tmp_path):
     """csrc/resample_tables.h in a program of its own (tests/resample_tables_main.cpp), plain and with
-    -fsanitize=address,undefined: both run clean over the size list and the edges of what is
-    supported, print the same sums, and those are the sums of the tables libisr hands to Python."""
-    out = {}
-    for tag, extra in (("plain", []), ("san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                               "-fno-omit-frame-pointer"])):
-        exe = tmp_path / f"tables_{tag}"
-        cmd = [GXX, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", *extra, "-I",
-               str(ROOT / "image_super_resolution_amd" / "csrc"), str(ROOT / "tests" / "resample_tables_main.cpp"),
-               "-o", str(exe)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        args = [str(v) for f in range(6) for io in AXES for v in (f, *io)]
-        for run in ([str(exe)], [str(exe), *args]):
-            r = subprocess.run(run, capture_output=True, text=True, timeout=300)
-            assert r.returncode == 0 and not r.stderr.strip(), r.stdout[-1000:] + r.stderr[-4000:]
-            out.setdefault(tag, []).append(r.stdout)
-    assert out["plain"] == out["san"], "the sanitizer build computes something else"
-    sweep, listed = out["plain"]
+    -fsanitize=address,undefined (tests/host_program.py): both run clean over the size list and the
+    edges of what is supported, print the same sums, and those are the sums of the tables libisr
+    hands to Python."""
+    args = [str(v) for f in range(6) for io in AXES for v in (f, *io)]
+    sweep, listed = host_program.run_plain_and_sanitized(ROOT / "tests" / "resample_tables_main.cpp", tmp_path,
+                                                         runs=((), args))
     rows = [tuple(int(v) for v in line.split()) for line in (sweep + listed).splitlines()]
     assert len(rows) == 8 * 21 + 6 * len(AXES)
     assert {r[3] for r in rows} == {0, 1, 2, 3}  # accepted, and refused for each of the three reasons

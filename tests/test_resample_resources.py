@@ -3,8 +3,6 @@ it must compile for gfx950 without scratch and without VGPR spills, and its stat
 the largest supported ratio, lanczos at 8) must leave room for at least two blocks per CU: no more
 than half of a CU's 160 KiB."""
 import os
-import re
-import subprocess
 
 import pytest
 
@@ -13,27 +11,9 @@ from image_super_resolution_amd import _build
 CU_LDS_BYTES = 160 * 1024
 
 
-def _resources():
-    cmd = [_build.HIPCC, *_build.FLAGS, "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-           str(_build.CSRC / "resample.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: (.*) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        key, _, val = m.group(1).strip().partition(":")
-        if key == "Function Name":
-            cur = out.setdefault(val.strip(), {})
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return out
-
-
 @pytest.mark.skipif(not os.path.exists(_build.HIPCC), reason="needs hipcc")
 def test_resample_kernel_resources():
-    res = {k: v for k, v in _resources().items() if "resample_u8_kernel" in k}
+    res = {k: v for k, v in _build.kernel_resources(_build.CSRC / "resample.hip").items() if "resample_u8_kernel" in k}
     assert len(res) == 1, f"resample_u8_kernel not found: {sorted(res)}"
     (r,) = res.values()
     print(f"resample_u8_kernel: VGPRs {r['VGPRs']}, TotalSGPRs {r['TotalSGPRs']}, LDS {r['LDS Size [bytes/block]']} B, "

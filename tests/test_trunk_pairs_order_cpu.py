@@ -3,45 +3,28 @@ host-only program (tests/trunk_pairs_order_sim.cpp) includes the rule header and
 workgroup streams with blocking neighbourhood waits over a sweep of (n, nbx, nby, G).  Every
 geometry the rule accepts must run to completion pair-major, and unpaired as well; and some geometry
 the rule refuses must deadlock when paired (the rule is not vacuous).  The program is built plain and with the address and undefined-behaviour
-sanitizers; both must agree."""
-import shutil
-import subprocess
+sanitizers; both must agree (tests/host_program.py)."""
 from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-SRC = ROOT / "tests" / "trunk_pairs_order_sim.cpp"
-CSRC = ROOT / "image_super_resolution_amd" / "csrc"
-GXX = shutil.which("g++")
+import host_program
+
+SRC = Path(__file__).resolve().parent / "trunk_pairs_order_sim.cpp"
 
 
-def _sweep(tmp_path, name, extra):
-    exe = tmp_path / name
-    cmd = [GXX, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", *extra, "-I", str(CSRC), str(SRC), "-o",
-           str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert not r.stderr.strip(), r.stderr[-4000:]
-    rows = [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
+@pytest.fixture(scope="module")
+def sweep(tmp_path_factory):
+    if host_program.GXX is None:
+        pytest.skip("needs g++")
+    (out,) = host_program.run_plain_and_sanitized(SRC, tmp_path_factory.mktemp("pairs_order"), timeout=600)
+    rows = [tuple(int(v) for v in line.split()) for line in out.splitlines()]
     assert rows and all(len(row) == 7 for row in rows)
     return rows
 
 
-@pytest.fixture(scope="module")
-def sweeps(tmp_path_factory):
-    if GXX is None:
-        pytest.skip("needs g++")
-    d = tmp_path_factory.mktemp("pairs_order")
-    return (_sweep(d, "sim", []),
-            _sweep(d, "sim_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]))
-
-
-def test_accepted_geometries_complete_and_a_refused_one_deadlocks(sweeps):
-    plain, san = sweeps
-    assert plain == san, "the sanitizer build computes something else"
+def test_accepted_geometries_complete_and_a_refused_one_deadlocks(sweep):
+    plain = sweep
     accepted = [r for r in plain if r[4]]
     refused = [r for r in plain if not r[4]]
     print(f"{len(plain)} geometries: {len(accepted)} accepted, {len(refused)} refused, "

@@ -4,7 +4,6 @@ without VGPR spills, at 2 waves per SIMD (two 4-wave workgroups per CU).  The SG
 (SGPRs parked in VGPR lanes) is printed; DESIGN.md section 5 carries the figure."""
 import os
 import re
-import subprocess
 
 import pytest
 
@@ -14,22 +13,8 @@ PROD = re.compile(r"trunk_kernelILb([01])EEE")
 
 
 def _resource_lines():
-    cmd = [_build.HIPCC, *_build.FLAGS, "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-           str(_build.CSRC / "trunk.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: (.*) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        key, _, val = m.group(1).strip().partition(":")
-        if key == "Function Name":
-            k = PROD.search(val)
-            cur = out.setdefault("fp16" if k.group(1) == "1" else "bf16", {}) if k else None
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return out
+    found = ((PROD.search(name), r) for name, r in _build.kernel_resources(_build.CSRC / "trunk.hip").items())
+    return {"fp16" if k.group(1) == "1" else "bf16": r for k, r in found if k}
 
 
 @pytest.mark.skipif(not os.path.exists(_build.HIPCC), reason="needs hipcc")

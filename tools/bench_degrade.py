@@ -19,12 +19,10 @@ from __future__ import annotations
 
 import argparse
 import ctypes
+import functools
 import io
 import json
-import statistics
-import subprocess
 import sys
-import time
 from pathlib import Path
 
 import numpy as np
@@ -32,46 +30,28 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+import _timing  # noqa: E402
 from image_super_resolution_amd import _lib, data, degrade  # noqa: E402
 
-
-def timed(fn, iters: int, runs: int, warmup: int = 5) -> float:
-    """Median over `runs` of the µs per call of `fn` (device events around `iters` calls)."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(1e3 * e0.elapsed_time(e1) / iters)
-    return round(statistics.median(out), 2)
+timed = functools.partial(_timing.timed, warmup=5)
 
 
 def pil_roundtrip_ms(x: np.ndarray, q: np.ndarray, runs: int) -> float:
     from PIL import Image
     hwc = np.ascontiguousarray(x.transpose(0, 2, 3, 1))
-    ts = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
+
+    def roundtrip():
         for im, qi in zip(hwc, q):
             buf = io.BytesIO()
             Image.fromarray(im).save(buf, format="JPEG", quality=int(qi))
             buf.seek(0)
             np.asarray(Image.open(buf).convert("RGB"))
-        ts.append(time.perf_counter() - t0)
-    return round(1e3 * statistics.median(ts), 3)
+    return _timing.host_ms(roundtrip, runs)
 
 
 def train_step_ms(batch: int, size: int) -> float:
-    r = subprocess.run([sys.executable, str(ROOT / "tools" / "bench_denoise.py"), "--batch", "1", "--size", "96",
-                        "--train-batch", str(batch), "--train-size", str(size)], capture_output=True, text=True,
-                       check=True, timeout=600)
-    return json.loads(r.stdout.strip().splitlines()[-1])["train_step_ms"]
+    return _timing.train_step_ms("bench_denoise.py", ("--batch", "1", "--size", "96", "--train-batch", str(batch),
+                                                      "--train-size", str(size)), "train_step_ms", timeout=600)
 
 
 def case(n: int, t: int, iters: int, runs: int) -> dict:

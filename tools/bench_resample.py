@@ -25,10 +25,7 @@ from __future__ import annotations
 import argparse
 import ctypes
 import json
-import statistics
-import subprocess
 import sys
-import time
 from pathlib import Path
 
 import numpy as np
@@ -36,45 +33,17 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+from _timing import host_ms, timed, train_step_ms  # noqa: E402
 from image_super_resolution_amd import _lib, data, degrade  # noqa: E402
 
 HBM_PEAK_BYTES_PER_S = 8.0e12  # MI355X HBM3E, spec
-
-
-def timed(fn, iters: int, runs: int, warmup: int = 10) -> float:
-    """Median over `runs` of the µs per call of `fn` (device events around `iters` calls)."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(1e3 * e0.elapsed_time(e1) / iters)
-    return round(statistics.median(out), 2)
 
 
 def pil_resize_ms(x: np.ndarray, size: int, name: str, runs: int) -> float:
     from PIL import Image
     flt = getattr(Image, name.upper())
     ims = [Image.fromarray(np.ascontiguousarray(im.transpose(1, 2, 0))) for im in x]
-    ts = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        for im in ims:
-            im.resize((size, size), flt).load()
-        ts.append(time.perf_counter() - t0)
-    return round(1e3 * statistics.median(ts), 3)
-
-
-def train_step_ms() -> float:
-    r = subprocess.run([sys.executable, str(ROOT / "tools" / "bench_train.py"), "--steps", "3", "--warmup", "2"],
-                       capture_output=True, text=True, check=True, timeout=900)
-    return json.loads(r.stdout.strip().splitlines()[-1])["ms_per_step"]
+    return host_ms(lambda: [im.resize((size, size), flt).load() for im in ims], runs)
 
 
 def case(n: int, t: int, scale: int, iters: int, runs: int, empty_us: float) -> dict:

@@ -32,15 +32,8 @@ from __future__ import annotations
 
 import argparse
 import re
-import subprocess
 import sys
-import tempfile
 from pathlib import Path
-
-ROOT = Path(__file__).resolve().parents[1]
-HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-I", str(ROOT / "include"),
-         "-I", str(ROOT / "image_super_resolution_amd" / "csrc")]
 
 REG = re.compile(r"\b([va])(?:\[(\d+):(\d+)\]|(\d+)\b)")
 KERNEL = re.compile(r"^(_Z\w+):\s*(;.*)?$")
@@ -217,16 +210,6 @@ def kernels(asm: str):
     return out, scratch
 
 
-def device_asm(src: Path, extra: list[str]) -> str:
-    with tempfile.TemporaryDirectory() as td:
-        out = Path(td) / (src.stem + ".s")
-        r = subprocess.run([HIPCC, *FLAGS, *extra, "--cuda-device-only", "-S", str(src), "-o", str(out)],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc -S failed on {src}:\n{r.stderr}")
-        return out.read_text()
-
-
 def check_asm(asm: str, label: str, verbose: bool = False) -> list[str]:
     ks, scratch = kernels(asm)
     errors = []
@@ -250,8 +233,11 @@ def main(argv=None) -> int:
     ap.add_argument("-v", "--verbose", action="store_true")
     a = ap.parse_args(argv)
     errors = []
+    if a.sources:  # the library's compiler and flags (_build.device_asm)
+        sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+        from image_super_resolution_amd import _build
     for s in a.sources:
-        errors += check_asm(device_asm(Path(s), [f"-D{d}" for d in a.D]), Path(s).name, a.verbose)
+        errors += check_asm(_build.device_asm(Path(s).resolve(), [f"-D{d}" for d in a.D]), Path(s).name, a.verbose)
     for f in a.asm:
         errors += check_asm(Path(f).read_text(), Path(f).name, a.verbose)
     for e in errors:

@@ -35,13 +35,7 @@ RESOURCE = re.compile(r"^; (NumSgprs|NumVgprs|NumAgprs|TotalNumVgprs|ScratchSize
 
 def device_asm(root: Path, src: str, defines: list[str], out: Path) -> str:
     if not out.exists():
-        flags = [str(root / "include") if f == str(ROOT / "include") else
-                 str(root / "image_super_resolution_amd" / "csrc") if f == str(_build.CSRC) else f for f in _build.FLAGS]
-        cmd = [_build.HIPCC, *flags, *defines, "--cuda-device-only", "-S",
-               str(root / "image_super_resolution_amd" / "csrc" / src), "-o", str(out)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed on {root}/{src}:\n{r.stderr}")
+        out.write_text(_build.device_asm(root / "image_super_resolution_amd" / "csrc" / src, defines, root=root))
     return out.read_text()
 
 

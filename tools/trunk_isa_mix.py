@@ -17,9 +17,7 @@ from __future__ import annotations
 
 import argparse
 import re
-import subprocess
 import sys
-import tempfile
 from collections import Counter
 from pathlib import Path
 
@@ -53,21 +51,6 @@ def classify(op: str) -> str | None:
     if op.startswith("s_"):
         return "salu"
     return None
-
-
-def device_asm(csrc: Path, defines: list[str]) -> tuple[str, str]:
-    """(assembly text, compiler remarks) of trunk.hip in `csrc`."""
-    flags = [f for f in _build.FLAGS]
-    i = flags.index(str(_build.CSRC))
-    flags[i] = str(csrc)
-    with tempfile.TemporaryDirectory() as td:
-        out = Path(td) / "trunk.s"
-        cmd = [_build.HIPCC, *flags, *defines, "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-               str(csrc / "trunk.hip"), "-o", str(out)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{r.stderr}")
-        return out.read_text(), r.stderr
 
 
 def kernels(asm: str) -> dict[str, list[str]]:
@@ -157,28 +140,13 @@ def store_blocks(lines: list[str]) -> list[dict]:
     return res
 
 
-def resources(remarks: str) -> dict[str, list[str]]:
-    out, cur = {}, None
-    for line in remarks.splitlines():
-        m = re.search(r"remark: (.*) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        t = m.group(1).strip()
-        if t.startswith("Function Name:"):
-            name = t.split(":", 1)[1].strip()
-            cur = out.setdefault(name, []) if PROD.match(name) else None
-        elif cur is not None:
-            cur.append(t)
-    return out
-
-
 def storage_of(name: str) -> str:
     return "fp16" if PROD.match(name).group(1) == "1" else "bf16"
 
 
 def production_store_blocks(csrc: Path = _build.CSRC, defines: tuple[str, ...] = ()) -> dict[str, list[dict]]:
     """storage ("fp16" / "bf16") -> store_blocks() of that production instantiation."""
-    asm, _ = device_asm(Path(csrc).resolve(), list(defines))
+    asm = _build.device_asm(Path(csrc).resolve() / "trunk.hip", defines)
     return {storage_of(name): store_blocks(lines) for name, lines in kernels(asm).items()}
 
 
@@ -198,8 +166,9 @@ def main() -> int:
     ap.add_argument("-D", dest="defines", action="append", default=[])
     ap.add_argument("--all-blocks", action="store_true", help="list every basic block, not only MFMA / VMEM ones")
     a = ap.parse_args()
-    asm, remarks = device_asm(a.csrc.resolve(), [f"-D{d}" for d in a.defines])
-    res = resources(remarks)
+    src, defines = a.csrc.resolve() / "trunk.hip", [f"-D{d}" for d in a.defines]
+    asm, remarks = _build.device_asm(src, defines, remarks=True)
+    res = _build.kernel_resources(src, defines, remarks=remarks)
     ks = kernels(asm)
     if not ks:
         print("no production trunk_kernel instantiation found", file=sys.stderr)
@@ -208,8 +177,8 @@ def main() -> int:
         storage = storage_of(name)
         bl = blocks(lines)
         print(f"== {name} ({storage} storage)")
-        for t in res.get(name, []):
-            print(f"   {t}")
+        for field, value in res.get(name, {}).items():
+            print(f"   {field}: {value}")
         print(f"   basic blocks: {len(bl)}")
         print(f"   {'block':>12} " + " ".join(f"{c:>6}" for c in CLASSES))
         total = Counter()
