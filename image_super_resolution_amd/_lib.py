@@ -135,6 +135,12 @@ class IsrBlurDesc(ctypes.Structure):
                 ("ksize", c_void_p), ("median", c_void_p), ("taps", c_void_p)]
 
 
+class IsrYuvDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("layout", c_int32), ("siting", c_int32),
+                ("full_range", c_int32), ("fwd", c_int32 * 9), ("inv", c_int32 * 5), ("src", c_void_p),
+                ("dst", c_void_p)]
+
+
 HLS_PARTIAL_BLOCKS = 32  # ISR_HLS_PARTIAL_BLOCKS
 MT_TENSOR_BYTES = 40 # isr_mt_tensor: 4 pointers + int64
 MT_CHUNK_BYTES = 16   # isr_mt_chunk: int32 t, int32 len, int64 start
@@ -214,6 +220,9 @@ SIGNATURES = {
     "isr_resample_u8": (c_int32, [POINTER(IsrResampleDesc), c_void_p]),
     "isr_blur_taps": (c_int32, [c_int32, c_int32, c_void_p, c_void_p]),
     "isr_blur_u8": (c_int32, [POINTER(IsrBlurDesc), c_void_p]),
+    "isr_yuv_coeffs": (c_int32, [c_int32, c_int32, c_void_p, c_void_p]),
+    "isr_yuv420_to_rgb_u8": (c_int32, [POINTER(IsrYuvDesc), c_void_p]),
+    "isr_rgb_to_yuv420_u8": (c_int32, [POINTER(IsrYuvDesc), c_void_p]),
     "isr_last_error": (ctypes.c_char_p, []),
     "isr_version": (c_int32, []),
 }

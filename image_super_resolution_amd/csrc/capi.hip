@@ -9,6 +9,7 @@
 #include "isr_common.h"
 #include "blur_taps.h"
 #include "resample_tables.h"
+#include "yuv_coeffs.h"
 
 namespace isr {
 int conv3x3_fwd_dispatch(const isr_conv_desc* d, hipStream_t s);
@@ -62,6 +63,7 @@ int hls_l_moments_dispatch(const isr_hls_moments_desc* d, hipStream_t s);
 int iso_noise_dispatch(const isr_iso_noise_desc* d, hipStream_t s);
 int resample_u8_dispatch(const isr_resample_desc* d, hipStream_t s);
 int blur_u8_dispatch(const isr_blur_desc* d, hipStream_t s);
+int yuv_dispatch(const isr_yuv_desc* d, int to_rgb, hipStream_t s);
 }  // namespace isr
 
 static thread_local char g_err[512] = "";
@@ -863,6 +865,40 @@ int isr_blur_u8(const isr_blur_desc* d, isr_stream_t s) {
     const int rc = isr::blur_u8_dispatch(d, (hipStream_t)s);
     if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "blur_u8: more than 2^31 - 1 workgroups");
     return launched(rc, "blur_u8");
+}
+
+int isr_yuv_coeffs(int matrix, int full_range, int32_t* fwd, int32_t* inv) {
+    if (!fwd || !inv) return fail(ISR_ERR_BAD_DESC, "yuv_coeffs: null fwd / inv");
+    if (isr::yuv_coeffs(matrix, full_range, fwd, inv))
+        return fail(ISR_ERR_UNSUPPORTED, "yuv_coeffs: unknown matrix %d (ISR_YUV_BT601, BT709 = 0, 1)", matrix);
+    g_err[0] = 0;
+    return ISR_OK;
+}
+
+static int yuv_ok(const char* what, const isr_yuv_desc* d) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "%s: null descriptor", what);
+    if (!d->src || !d->dst) return fail(ISR_ERR_BAD_DESC, "%s: null src / dst", what);
+    if (d->dst == d->src) return fail(ISR_ERR_BAD_DESC, "%s: dst must not be src", what);
+    if (int rc = batch_ok(what, d->n, d->h, d->w, false)) return rc;
+    if (d->h < 2 || d->w < 2 || d->h % 2 || d->w % 2)
+        return fail(ISR_ERR_BAD_DESC, "%s: 4:2:0 needs even h and w of at least 2, got %dx%d", what, d->h, d->w);
+    if ((long long)d->h * d->w > (1ll << 28))
+        return fail(ISR_ERR_UNSUPPORTED, "%s: h*w = %lld is more than 2^28", what, (long long)d->h * d->w);
+    if (d->layout != ISR_YUV_I420 && d->layout != ISR_YUV_NV12)
+        return fail(ISR_ERR_UNSUPPORTED, "%s: unknown layout %d (ISR_YUV_I420, NV12 = 0, 1)", what, d->layout);
+    if (d->siting != ISR_YUV_SITING_LEFT && d->siting != ISR_YUV_SITING_CENTER)
+        return fail(ISR_ERR_UNSUPPORTED, "%s: unknown siting %d (ISR_YUV_SITING_LEFT, CENTER = 0, 1)", what, d->siting);
+    return ISR_OK;
+}
+
+int isr_yuv420_to_rgb_u8(const isr_yuv_desc* d, isr_stream_t s) {
+    if (int rc = yuv_ok("yuv420_to_rgb_u8", d)) return rc;
+    return launched(isr::yuv_dispatch(d, 1, (hipStream_t)s), "yuv420_to_rgb_u8");
+}
+
+int isr_rgb_to_yuv420_u8(const isr_yuv_desc* d, isr_stream_t s) {
+    if (int rc = yuv_ok("rgb_to_yuv420_u8", d)) return rc;
+    return launched(isr::yuv_dispatch(d, 0, (hipStream_t)s), "rgb_to_yuv420_u8");
 }
 
 }  // extern "C"

@@ -17,7 +17,12 @@ encoder, bitrate ∝ output megapixels) — rebuilt around the MI355X path:
 * decode / encode use the ffmpeg binary through raw pipes when it is installed
   (as the reference does); `RawVideoReader` / `RawRecorder` read and write
   headerless rgb24 / bgr24 files and `SyntheticVideo` generates frames, so the
-  pipeline is testable and benchmarkable on a machine without ffmpeg.
+  pipeline is testable and benchmarkable on a machine without ffmpeg;
+* opt-in, frames cross the host boundary as 8-bit YUV 4:2:0 (`pix_fmt_in` / `pix_fmt_out` of
+  yuv420p or nv12: half the bytes of rgb24 / bgr24, what decoders produce and encoders take) and the
+  colour conversion runs in the captured graph (yuv.py, csrc/yuv.hip) in place of the layout copies;
+  `Y4MReader` / `Y4MRecorder` read and write YUV4MPEG2 (.y4m) files, `RawYUVReader` headerless
+  I420 / NV12, again without ffmpeg.
 
 Reference bugs deliberately not reproduced: the frame is
 normalised once (rs.py:63 normalises before a TorchScript Model that normalises
@@ -27,6 +32,7 @@ DataLoader uses shuffle=True but `__getitem__` ignores the index).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import platform
 import queue
@@ -34,13 +40,17 @@ import shutil
 import subprocess
 import threading
 from pathlib import Path
+from fractions import Fraction
 from typing import Iterator
 
 import numpy as np
 import torch
 
-from . import engine
+from . import _lib, engine, yuv as yuvmod
+from .yuv import YUVFormat
 
+RGB_FORMATS = (".rgb", ".raw", ".rgb24")       # headerless rgb24 input
+YUV_FORMATS = (".y4m", ".yuv", ".i420", ".nv12")  # YUV4MPEG2 and headerless I420 / NV12 input
 VID_FORMATS = ('.mp4', '.avi', '.mkv', '.mov', '.wmv', '.flv', '.webm', '.mpeg', '.mpg', '.m4v', '.ts')
 
 
@@ -49,14 +59,39 @@ def have_ffmpeg() -> bool:
 
 
 # ----------------------------------------------------------------------------- sources
+def ffmpeg_reader_cmd(src: str | Path, pix_fmt: str = "rgb24") -> list[str]:
+    """FFmpegVideoReader's decoder argv: raw frames of `pix_fmt` (rgb24, yuv420p or nv12) to a pipe."""
+    if pix_fmt != "rgb24" and pix_fmt not in yuvmod.PIX_FMTS:
+        raise ValueError(f"unknown pix_fmt {pix_fmt!r}; rgb24, {', '.join(yuvmod.PIX_FMTS)}")
+    return ["ffmpeg", "-v", "quiet", "-i", Path(src).as_posix(), "-f", "rawvideo", "-pix_fmt", pix_fmt, "pipe:"]
+
+
 class FFmpegVideoReader:
     """Decoded uint8 HWC RGB frames of a video file via an ffmpeg rawvideo pipe
     (the role of torchvision's VideoReader in utils/datasets.py:431-453)."""
 
-    def __init__(self, src: str | Path):
+    def __init__(self, src: str | Path, pix_fmt: str = "rgb24", meta: dict | None = None):
+        """`meta` (width, height and optionally fps, frames) stands in for the ffprobe call: the reader
+        is then made without the binaries, which only iterating needs."""
+        self.cmd = ffmpeg_reader_cmd(src, pix_fmt)
+        self.pix_fmt = pix_fmt
+        src = Path(src)
+        if meta is not None:
+            self.width, self.height = int(meta["width"]), int(meta["height"])
+            self.fps, self.total_frame = float(meta.get("fps", 30.0)), int(meta.get("frames", 0))
+        else:
+            self._probe(src)
+        self.src = src
+        self.yuv = None
+        self.frame_shape = (self.height, self.width, 3)
+        if pix_fmt != "rgb24":  # frames as [3h/2, w] bytes; the stream's own tags are not read: YUVFormat's defaults
+            self.yuv = YUVFormat.of_pix_fmt(pix_fmt)
+            yuvmod.check_size(self.height, self.width)
+            self.frame_shape = (3 * self.height // 2, self.width)
+
+    def _probe(self, src: Path) -> None:
         if not have_ffmpeg():
             raise RuntimeError("FFmpegVideoReader needs the ffmpeg and ffprobe binaries")
-        src = Path(src)
         probe = subprocess.run(["ffprobe", "-v", "error", "-select_streams", "v:0", "-show_entries",
                                 "stream=width,height,r_frame_rate,nb_frames,duration", "-of",
                                 "default=noprint_wrappers=1", src.as_posix()],
@@ -68,21 +103,19 @@ class FFmpegVideoReader:
         nb = meta.get("nb_frames", "N/A")
         dur = meta.get("duration", "N/A")
         self.total_frame = int(nb) if nb.isdigit() else (int(self.fps * float(dur)) if dur != "N/A" else 0)
-        self.src = src
 
     def __len__(self):
         return self.total_frame
 
     def __iter__(self) -> Iterator[np.ndarray]:
-        cmd = ["ffmpeg", "-v", "quiet", "-i", self.src.as_posix(), "-f", "rawvideo", "-pix_fmt", "rgb24", "pipe:"]
-        proc = subprocess.Popen(cmd, stdout=subprocess.PIPE)
-        n = self.width * self.height * 3
+        proc = subprocess.Popen(self.cmd, stdout=subprocess.PIPE)
+        n = math.prod(self.frame_shape)
         try:
             while True:
                 buf = proc.stdout.read(n)
                 if len(buf) < n:
                     break
-                yield np.frombuffer(buf, np.uint8).reshape(self.height, self.width, 3)
+                yield np.frombuffer(buf, np.uint8).reshape(self.frame_shape)
         finally:
             proc.stdout.close()
             proc.wait()
@@ -108,6 +141,112 @@ class RawVideoReader:
             yield np.asarray(mm[i])
 
 
+Y4M_MAGIC = b"YUV4MPEG2"
+Y4M_SITING = {"420jpeg": "center", "420": "center", "420mpeg2": "left"}  # the C tag's value -> chroma siting
+Y4M_TAG = {"center": "420jpeg", "left": "420mpeg2"}
+
+
+def y4m_header(width: int, height: int, fps, yuv: YUVFormat) -> bytes:
+    """The YUV4MPEG2 stream header of progressive 8-bit 4:2:0 frames in `yuv`'s siting and range."""
+    yuvmod.check_size(height, width)
+    if yuv.layout != "i420":
+        raise ValueError("a .y4m file holds planar I420 frames, not NV12")
+    rate = Fraction(fps).limit_denominator(1001)
+    rng = "FULL" if yuv.full_range else "LIMITED"
+    return (f"YUV4MPEG2 W{width} H{height} F{rate.numerator}:{rate.denominator} Ip A1:1 C{Y4M_TAG[yuv.siting]} "
+            f"XCOLORRANGE={rng}\n").encode("ascii")
+
+
+def parse_y4m_header(line: bytes) -> dict:
+    """width, height, fps and yuv (a YUVFormat, matrix "auto") of a YUV4MPEG2 header line.  8-bit
+    progressive 4:2:0 only: any other C or I tag raises a ValueError naming it."""
+    tags = line.decode("ascii", "replace").split()
+    if not tags or tags[0] != Y4M_MAGIC.decode():
+        raise ValueError("not a YUV4MPEG2 stream (no YUV4MPEG2 magic)")
+    w = h = None
+    fps, siting, full = 30.0, "center", False
+    for t in tags[1:]:
+        k, v = t[0], t[1:]
+        if k == "W":
+            w = int(v)
+        elif k == "H":
+            h = int(v)
+        elif k == "F":
+            num, _, den = v.partition(":")
+            fps = float(num) / float(den or 1) if float(den or 1) else 30.0
+        elif k == "I":
+            if v not in ("p", "?"):
+                raise ValueError(f"y4m: interlacing tag {t!r} is not supported (progressive Ip / I? only)")
+        elif k == "C":
+            if v not in Y4M_SITING:
+                raise ValueError(f"y4m: chroma tag {t!r} is not supported (8-bit C420jpeg, C420, C420mpeg2 only)")
+            siting = Y4M_SITING[v]
+        elif t.startswith("XCOLORRANGE="):
+            full = t.split("=", 1)[1].upper() == "FULL"
+    if w is None or h is None:
+        raise ValueError("y4m: the header has no W / H tag")
+    yuvmod.check_size(h, w)
+    return {"width": w, "height": h, "fps": fps, "yuv": YUVFormat("i420", "auto", full, siting)}
+
+
+class Y4MReader:
+    """The frames of a YUV4MPEG2 (.y4m) file as uint8 [3h/2, w] arrays (a frame's bytes in order: the Y
+    plane's rows, then U, then V).  `yuv` holds the header's siting and range; a truncated last frame
+    ends the stream."""
+    pix_fmt = "yuv420p"
+
+    def __init__(self, src: str | Path):
+        self.src = Path(src)
+        with open(self.src, "rb") as f:
+            line = f.readline(4096)
+            self._data0 = f.tell()
+        meta = parse_y4m_header(line)
+        self.width, self.height, self.fps, self.yuv = meta["width"], meta["height"], meta["fps"], meta["yuv"]
+        self.frame_shape = (3 * self.height // 2, self.width)
+        # "FRAME\n" carries no parameters in the files encoders write: the count is exact for those
+        self.total_frame = (self.src.stat().st_size - self._data0) // (math.prod(self.frame_shape) + 6)
+
+    def __len__(self):
+        return self.total_frame
+
+    def __iter__(self) -> Iterator[np.ndarray]:
+        n = math.prod(self.frame_shape)
+        with open(self.src, "rb") as f:
+            f.seek(self._data0)
+            while True:
+                head = f.readline(4096)
+                if not head.startswith(b"FRAME"):
+                    break
+                buf = f.read(n)
+                if len(buf) < n:
+                    break
+                yield np.frombuffer(buf, np.uint8).reshape(self.frame_shape)
+
+
+class RawYUVReader:
+    """Headerless 4:2:0 frames (I420 or NV12, 3 h w / 2 bytes each, back to back) from a file, as uint8
+    [3h/2, w] arrays."""
+
+    def __init__(self, src: str | Path, width: int, height: int, fps: float = 30.0, layout: str = "i420"):
+        self.src, self.width, self.height, self.fps = Path(src), width, height, fps
+        self.yuv = YUVFormat(layout)
+        self.pix_fmt = self.yuv.pix_fmt
+        fb = yuvmod.frame_bytes(height, width)
+        size = self.src.stat().st_size
+        if size % fb:
+            raise ValueError(f"{src}: {size} bytes is not a whole number of {width}x{height} 4:2:0 frames")
+        self.total_frame = size // fb
+        self.frame_shape = (3 * height // 2, width)
+
+    def __len__(self):
+        return self.total_frame
+
+    def __iter__(self) -> Iterator[np.ndarray]:
+        mm = np.memmap(self.src, np.uint8, "r", shape=(self.total_frame, *self.frame_shape))
+        for i in range(self.total_frame):
+            yield np.asarray(mm[i])
+
+
 class SyntheticVideo:
     """`frames` smooth moving uint8 RGB frames (benchmarks / tests; no decoder)."""
 
@@ -128,14 +267,23 @@ class SyntheticVideo:
             yield f + self._noise
 
 
-def open_video(src: str | Path, width: int | None = None, height: int | None = None, fps: float = 30.0):
-    """`dataset_for_inference` equivalent: ffmpeg for container formats, raw for .rgb/.raw."""
+def open_video(src: str | Path, width: int | None = None, height: int | None = None, fps: float = 30.0,
+               pix_fmt: str = "rgb24"):
+    """`dataset_for_inference` equivalent: ffmpeg for container formats (decoding to `pix_fmt`), raw for
+    .rgb/.raw, YUV4MPEG2 for .y4m, headerless I420 for .yuv/.i420 and NV12 for .nv12."""
     src = Path(src)
-    if src.suffix.lower() in (".rgb", ".raw", ".rgb24"):
+    suffix = src.suffix.lower()
+    if suffix in RGB_FORMATS:
         if not (width and height):
             raise ValueError("raw rgb24 input needs --video_size WxH")
         return RawVideoReader(src, width, height, fps)
-    return FFmpegVideoReader(src)
+    if suffix == ".y4m":
+        return Y4MReader(src)
+    if suffix in YUV_FORMATS:
+        if not (width and height):
+            raise ValueError("raw 4:2:0 input needs --video_size WxH")
+        return RawYUVReader(src, width, height, fps, "nv12" if suffix == ".nv12" else "i420")
+    return FFmpegVideoReader(src, pix_fmt)
 
 
 # ----------------------------------------------------------------------------- sinks
@@ -169,7 +317,7 @@ class FFMPEG_recorder:  # noqa: N801  (reference class name, utils/ffmpeg.py:28)
     for that platform), else libx264."""
 
     def __init__(self, save_path=None, videoDimensions=(1280, 720), fps=30, codec: str | None = None,
-                 dry_run: bool = False):
+                 dry_run: bool = False, pix_fmt: str = "bgr24", yuv: YUVFormat | None = None):
         self.save_path = save_path
         self.dimension = videoDimensions
         self.fps = fps
@@ -183,9 +331,20 @@ class FFMPEG_recorder:  # noqa: N801  (reference class name, utils/ffmpeg.py:28)
         self.bitRate = _bitrate_mbps(self.dimension, self.fps)
         self.subtitleContent = ''
         width, height = self.dimension
-        source = ['-s', f'{width}x{height}', '-pixel_format', 'bgr24', '-f', 'rawvideo', '-r', f'{self.fps}',
+        if pix_fmt != "bgr24" and pix_fmt not in yuvmod.PIX_FMTS:
+            raise ValueError(f"FFMPEG_recorder: pix_fmt {pix_fmt!r}: bgr24, {', '.join(yuvmod.PIX_FMTS)}")
+        self.pix_fmt, self.yuv = pix_fmt, None
+        tags = []
+        if pix_fmt != "bgr24":  # 4:2:0 frames through the pipe: ffmpeg converts nothing, so tell it what they are
+            self.yuv = (yuv or YUVFormat.of_pix_fmt(pix_fmt)).resolved(height)
+            if self.yuv.pix_fmt != pix_fmt:
+                raise ValueError(f"FFMPEG_recorder: pix_fmt {pix_fmt!r} with a {self.yuv.layout} YUVFormat")
+            tags = ['-colorspace', 'bt709' if self.yuv.matrix == 'bt709' else 'smpte170m',
+                    '-color_range', 'pc' if self.yuv.full_range else 'tv',
+                    '-chroma_sample_location', self.yuv.siting]
+        source = ['-s', f'{width}x{height}', '-pixel_format', pix_fmt, *tags, '-f', 'rawvideo', '-r', f'{self.fps}',
                   '-i', 'pipe:']
-        sink = ['-vcodec', f'{self.codec}', '-pix_fmt', 'yuv420p', '-b:v', f'{self.bitRate}M', f'{out_path}']
+        sink = ['-vcodec', f'{self.codec}', '-pix_fmt', 'yuv420p', *tags, '-b:v', f'{self.bitRate}M', f'{out_path}']
         self.cmd = ['ffmpeg', '-v', 'quiet', '-y', *source, *sink]
         self.process = None
         if dry_run:
@@ -195,7 +354,7 @@ class FFMPEG_recorder:  # noqa: N801  (reference class name, utils/ffmpeg.py:28)
         self.process = subprocess.Popen(self.cmd, stdin=subprocess.PIPE)
 
     def writeFrame(self, image=None):  # noqa: N802
-        """image: ndarray uint8 HWC BGR."""
+        """image: ndarray uint8 HWC BGR (or the [3h/2, w] bytes of a 4:2:0 frame of `pix_fmt`)."""
         self.process.stdin.write(np.ascontiguousarray(image).tobytes())
 
     @staticmethod
@@ -274,6 +433,36 @@ class RawRecorder:
         return 0
 
 
+class Y4MRecorder:
+    """Writes 4:2:0 I420 frames to a YUV4MPEG2 (.y4m) file, which ffmpeg, x264, x265, SVT-AV1 and aomenc
+    read: the header (size, rate, the C tag of `yuv`'s siting, XCOLORRANGE), then FRAME + the frame's
+    bytes."""
+
+    def __init__(self, save_path, videoDimensions=(1280, 720), fps=30, yuv: YUVFormat | None = None):  # noqa: N803
+        self.save_path, self.dimension, self.fps = str(save_path), videoDimensions, fps
+        self.yuv = yuv or YUVFormat()
+        width, height = videoDimensions
+        header = y4m_header(width, height, fps, self.yuv)
+        self._bytes = yuvmod.frame_bytes(height, width)
+        self._f = open(self.save_path, "wb")
+        self._f.write(header)
+        self.frames = 0
+
+    def writeFrame(self, image):  # noqa: N802
+        buf = np.ascontiguousarray(image).tobytes()
+        if len(buf) != self._bytes:
+            raise ValueError(f"Y4MRecorder: a frame of {len(buf)} bytes, expected {self._bytes}")
+        self._f.write(b"FRAME\n")
+        self._f.write(buf)
+        self.frames += 1
+
+    def stopRecorder(self):  # noqa: N802
+        self._f.close()
+
+    def addAudio(self, audio_src):  # noqa: N802
+        return 0
+
+
 class NullRecorder:
     """Counts frames (benchmarks: measures the pipeline without an encoder)."""
 
@@ -293,23 +482,49 @@ class NullRecorder:
 # ----------------------------------------------------------------------------- the GPU pipeline
 class FrameUpscaler:
     """uint8 HWC RGB frame batches → uint8 HWC BGR super-resolved frames on the
-    HIP generator, one captured HIP graph per batch geometry.
+    HIP generator, one captured HIP graph per batch geometry.  `pix_fmt_in` / `pix_fmt_out` of yuv420p
+    or nv12 (independently) make that side 8-bit 4:2:0 frames of `yuv_in` / `yuv_out` (a YUVFormat; by
+    default limited range, left siting, the matrix by the frame's height), converted by libisr's colour
+    kernels inside the same graph.
 
     `gw` is an engine.GeneratorWeights (tiler.runner_for(model).gw); `mean` /
     `std` the Normalize constants fused into the head kernel."""
 
     def __init__(self, gw: engine.GeneratorWeights, height: int, width: int, batch: int = 1, mean=(0.485, 0.456, 0.406),
-                 std=(0.229, 0.224, 0.225), device="cuda", graph: bool = True):
+                 std=(0.229, 0.224, 0.225), device="cuda", graph: bool = True, pix_fmt_in: str = "rgb24",
+                 pix_fmt_out: str = "bgr24", yuv_in: YUVFormat | None = None, yuv_out: YUVFormat | None = None):
+        if pix_fmt_in != "rgb24" and pix_fmt_in not in yuvmod.PIX_FMTS:
+            raise ValueError(f"pix_fmt_in {pix_fmt_in!r}: rgb24, {', '.join(yuvmod.PIX_FMTS)}")
+        if pix_fmt_out != "bgr24" and pix_fmt_out not in yuvmod.PIX_FMTS:
+            raise ValueError(f"pix_fmt_out {pix_fmt_out!r}: bgr24, {', '.join(yuvmod.PIX_FMTS)}")
         self.device = torch.device(device)
         self.batch, self.h, self.w = batch, height, width
         self.scale = 2 ** len(gw.scalers)
-        self.plan = engine.make_plan(gw, batch, height, width, self.device, True, True, mean, std)
+        self.pix_fmt_in, self.pix_fmt_out = pix_fmt_in, pix_fmt_out
         H, W = height * self.scale, width * self.scale
         self.out_hw = (H, W)
-        self.x_hwc = torch.zeros((batch, height, width, 3), dtype=torch.uint8, device=self.device)
+        # the 4:2:0 formats of the two sides, the matrix of each resolved by that side's own height
+        self.yuv_in = self.yuv_out = None
+        if pix_fmt_in != "rgb24":
+            self.yuv_in = self._format(yuv_in, pix_fmt_in, height, width)
+        if pix_fmt_out != "bgr24":
+            self.yuv_out = self._format(yuv_out, pix_fmt_out, H, W)
+        self.plan = engine.make_plan(gw, batch, height, width, self.device, True, True, mean, std)
+        self.in_frame_shape = (height, width, 3) if self.yuv_in is None else (3 * height // 2, width)
+        self.out_frame_shape = (H, W, 3) if self.yuv_out is None else (3 * H // 2, W)
+        self.x_in = torch.zeros((batch, *self.in_frame_shape), dtype=torch.uint8, device=self.device)
         self.x = torch.empty((batch, 3, height, width), dtype=torch.uint8, device=self.device)
         self.y = torch.empty(self.plan.out_shape, dtype=torch.uint8, device=self.device)
-        self.bgr = torch.empty((batch, H, W, 3), dtype=torch.uint8, device=self.device)
+        self.y_out = torch.empty((batch, *self.out_frame_shape), dtype=torch.uint8, device=self.device)
+        self.x_hwc = self.x_in if self.yuv_in is None else None  # the rgb-mode names of the staging tensors
+        self.bgr = self.y_out if self.yuv_out is None else None
+        self._lib = _lib.load()
+        self._desc_in = self._desc_out = None
+        with torch.cuda.device(self.device):
+            if self.yuv_in is not None:
+                self._desc_in = yuvmod._desc(batch, height, width, self.yuv_in, self.x_in.data_ptr(), self.x.data_ptr())
+            if self.yuv_out is not None:
+                self._desc_out = yuvmod._desc(batch, H, W, self.yuv_out, self.y.data_ptr(), self.y_out.data_ptr())
         self.stream = torch.cuda.Stream(self.device)
         self.graph = None
         with torch.cuda.stream(self.stream):
@@ -322,33 +537,50 @@ class FrameUpscaler:
                 self._body()
             self.stream.synchronize()
 
+    @staticmethod
+    def _format(fmt: YUVFormat | None, pix_fmt: str, height: int, width: int) -> YUVFormat:
+        fmt = fmt or YUVFormat.of_pix_fmt(pix_fmt)
+        if fmt.pix_fmt != pix_fmt:
+            raise ValueError(f"pix_fmt {pix_fmt!r} with a {fmt.layout} YUVFormat")
+        yuvmod.check_size(height, width)
+        return fmt.resolved(height)
+
     def _body(self):
-        self.x.copy_(self.x_hwc.permute(0, 3, 1, 2))
+        if self._desc_in is None:
+            self.x.copy_(self.x_in.permute(0, 3, 1, 2))
+        else:  # 4:2:0 frames -> planar RGB, one kernel in place of the HWC→CHW copy
+            _lib.check(self._lib.isr_yuv420_to_rgb_u8(ctypes.byref(self._desc_in), yuvmod._stream()),
+                       "isr_yuv420_to_rgb_u8")
         self.plan.run(self.x, self.y)
-        self.bgr.copy_(self.y.flip(1).permute(0, 2, 3, 1))  # RGB2BGR + CHW→HWC (utils/datasets.py RGB2BGR)
+        if self._desc_out is None:
+            self.y_out.copy_(self.y.flip(1).permute(0, 2, 3, 1))  # RGB2BGR + CHW→HWC (utils/datasets.py RGB2BGR)
+        else:  # planar RGB -> 4:2:0 frames, in place of the flip / permute copy
+            _lib.check(self._lib.isr_rgb_to_yuv420_u8(ctypes.byref(self._desc_out), yuvmod._stream()),
+                       "isr_rgb_to_yuv420_u8")
 
     def run_async(self):
-        """Forward of whatever x_hwc holds, on self.stream."""
+        """Forward of whatever x_in holds, on self.stream."""
         with torch.cuda.stream(self.stream):  # replay() launches on the current stream
             if self.graph is not None:
                 self.graph.replay()
             else:
                 self._body()
 
-    def __call__(self, frames_hwc: torch.Tensor) -> torch.Tensor:
-        """Synchronous convenience: uint8 [b,h,w,3] RGB (host or device) → device [b,H,W,3] BGR."""
-        b = frames_hwc.shape[0]
-        if b > self.batch or tuple(frames_hwc.shape[1:]) != (self.h, self.w, 3):
-            raise ValueError(f"frames {tuple(frames_hwc.shape)} do not fit the plan {(self.batch, self.h, self.w, 3)}")
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        """Synchronous convenience: uint8 [b,h,w,3] RGB (host or device) → device [b,H,W,3] BGR; with a
+        4:2:0 pix_fmt_in / pix_fmt_out that side is [b,3h/2,w] / [b,3H/2,W] frame bytes."""
+        b = frames.shape[0]
+        if b > self.batch or tuple(frames.shape[1:]) != self.in_frame_shape:
+            raise ValueError(f"frames {tuple(frames.shape)} do not fit the plan {(self.batch, *self.in_frame_shape)}")
         with torch.cuda.stream(self.stream):
-            self.x_hwc[:b].copy_(frames_hwc, non_blocking=True)
+            self.x_in[:b].copy_(frames, non_blocking=True)
             if b < self.batch:
-                self.x_hwc[b:].zero_()
+                self.x_in[b:].zero_()
         self.run_async()
         self.stream.synchronize()
         with torch.cuda.stream(self.stream):
             self.plan.verify()  # a persistent-chain give-up raises before the frames are handed out
-        return self.bgr[:b]
+        return self.y_out[:b]
 
 
 class VideoUpscaler:
@@ -359,10 +591,9 @@ class VideoUpscaler:
 
     def __init__(self, up: FrameUpscaler):
         self.up = up
-        b, h, w = up.batch, up.h, up.w
-        H, W = up.out_hw
-        self.pin_in = [torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.pin_out = [torch.empty((b, H, W, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        b = up.batch
+        self.pin_in = [torch.empty((b, *up.in_frame_shape), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.pin_out = [torch.empty((b, *up.out_frame_shape), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.h2d_done = [torch.cuda.Event(), torch.cuda.Event()]
         self.d2h_done = [torch.cuda.Event(), torch.cuda.Event()]
         # per output slot: the chains' give-up counts, copied right after that batch's forward
@@ -371,8 +602,9 @@ class VideoUpscaler:
         self.pin_state = [torch.zeros(max(1, len(self.chains)), dtype=torch.int32).pin_memory() for _ in range(2)]
 
     def run(self, frames, recorder, max_frames: int | None = None) -> int:
-        """Upscale every frame of `frames` (iterable of uint8 HWC RGB arrays) into
-        `recorder.writeFrame` (BGR HWC).  Returns the number of frames written."""
+        """Upscale every frame of `frames` (iterable of uint8 HWC RGB arrays, or of [3h/2, w] 4:2:0 frames
+        of the upscaler's pix_fmt_in) into `recorder.writeFrame` (BGR HWC, or a 4:2:0 frame of
+        pix_fmt_out).  Returns the number of frames written."""
         up, b = self.up, self.up.batch
         q: queue.Queue = queue.Queue()
         out_free = [threading.Event(), threading.Event()]
@@ -421,13 +653,13 @@ class VideoUpscaler:
                 out_free[slot].wait()  # the writer is done with batch i-2's output slot
                 out_free[slot].clear()
                 with torch.cuda.stream(up.stream):
-                    up.x_hwc.copy_(self.pin_in[slot], non_blocking=True)
+                    up.x_in.copy_(self.pin_in[slot], non_blocking=True)
                     self.h2d_done[slot].record(up.stream)
                 up.run_async()
                 with torch.cuda.stream(up.stream):
                     for k, c in enumerate(self.chains):
                         c.snapshot(self.pin_state[slot][k:k + 1])
-                    self.pin_out[slot].copy_(up.bgr, non_blocking=True)
+                    self.pin_out[slot].copy_(up.y_out, non_blocking=True)
                     self.d2h_done[slot].record(up.stream)
                 q.put((slot, n))
                 written += n

@@ -741,6 +741,79 @@ typedef struct isr_blur_desc {
 } isr_blur_desc;
 int isr_blur_u8(const isr_blur_desc* d, isr_stream_t s);
 
+/* ---- YUV 4:2:0 video frames ----------------------------------------------------
+ * 8-bit 4:2:0 Y'CbCr frames <-> planar uint8 RGB [n][3][h][w], in integer arithmetic from host-made
+ * coefficients: what a video source hands over and a video sink takes (the video path's
+ * FrameUpscaler.x / .y), in place of packed rgb24 / bgr24.  h and w even and at least 2.
+ *
+ * A frame is 3 h w / 2 bytes; a batch is n frames back to back.
+ *   ISR_YUV_I420   planes Y [h][w], U [h/2][w/2], V [h/2][w/2], back to back (ffmpeg's yuv420p)
+ *   ISR_YUV_NV12   plane Y [h][w], then [h/2] rows of w bytes U0 V0 U1 V1 ...
+ *
+ * isr_yuv_coeffs (host, plain C++, no GPU) makes the coefficients with ISR_YUV_BITS = 16 fractional
+ * bits: fix(v) = floor(v * 65536 + 0.5) of the exact fp64 value, one rounding per operation.
+ *   matrix  ISR_YUV_BT601 (Kr 0.299, Kb 0.114) or ISR_YUV_BT709 (Kr 0.2126, Kb 0.0722); Kg = 1 - Kr - Kb
+ *   range   limited (full_range 0): sy = 219/255, sc = 224/255, oy = 16; full: sy = sc = 1, oy = 0
+ *   fwd[9]  rows Y, Cb, Cr over (R, G, B):
+ *             Y  = sy (Kr, Kg, Kb)
+ *             Cb = sc (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb))
+ *             Cr = sc (1 - Kr, -Kg, -Kb) / (2 (1 - Kr))
+ *           The R and B entries are fix()ed; the G entry is then set so that the Y row sums to exactly
+ *           fix(sy) and each chroma row to exactly 0: a grey pixel gives Cb = Cr = 128.
+ *   inv[5]  cy = 1/sy, crv = 2 (1 - Kr) / sc, cbu = 2 (1 - Kb) / sc, cgu = -cbu Kb / Kg,
+ *           cgv = -crv Kr / Kg, in this order, each fix()ed.
+ * Refused: an unknown matrix ISR_ERR_UNSUPPORTED; a null pointer ISR_ERR_BAD_DESC.
+ *
+ * Chroma siting: ISR_YUV_SITING_LEFT (MPEG-2 / H.264 / HEVC: the chroma sample sits on the even luma
+ * column, midway between the two luma rows) or ISR_YUV_SITING_CENTER (JPEG / MPEG-1: the centre of the
+ * 2 x 2 block).  clamp8 clips to [0, 255]; >> is an arithmetic (flooring) shift; every stored value is
+ * rounded once.
+ *
+ * isr_rgb_to_yuv420_u8: src planar RGB [n][3][h][w] -> dst frames.
+ *   Y[y][x] = clamp8((fwdY . (R, G, B) + oy 65536 + 32768) >> 16)
+ *   C[i][j] = clamp8((fwdC . S + 128 65536 D + 32768 D) >> (16 + log2 D)), with S the integer footprint
+ *   sums of R, G and B:
+ *     center  the 2 x 2 block (rows 2i, 2i+1, columns 2j, 2j+1), D = 4
+ *     left    columns 2j-1, 2j, 2j+1 with weights 1, 2, 1 over rows 2i and 2i+1, D = 8; column -1
+ *             replicates column 0
+ *
+ * isr_yuv420_to_rgb_u8: src frames -> dst planar RGB [n][3][h][w].  Chroma is upsampled as integer
+ * numerators (indices past an edge replicate the edge):
+ *   horizontal, left    H[2j] = 2 C[j],            H[2j+1] = C[j] + C[j+1]
+ *   horizontal, center  H[2j] = 3 C[j] + C[j-1],   H[2j+1] = 3 C[j] + C[j+1]
+ *   vertical, both      row 2i = 3 H_i + H_(i-1),  row 2i+1 = 3 H_i + H_(i+1)
+ * giving U*, V* with D = 8 (left) or 16 (center); then
+ *   R = clamp8((cy D (Y - oy) + crv (V* - 128 D) + 32768 D) >> (16 + log2 D))
+ *   G = clamp8((cy D (Y - oy) + cgu (U* - 128 D) + cgv (V* - 128 D) + 32768 D) >> (16 + log2 D))
+ *   B = clamp8((cy D (Y - oy) + cbu (U* - 128 D) + 32768 D) >> (16 + log2 D))
+ * All sums fit int32 for the coefficients isr_yuv_coeffs makes (the largest is about 5.9e8; other
+ * coefficients wrap, they cannot make an access go wild).  Y outside [16, 235] and chroma of 0 or 255 are legal inputs: only the final clamp
+ * limits the result.
+ *
+ * Both are one launch on `s`, stateless: no device table, no workspace, no allocation, no
+ * synchronisation.  n in [1, 65535]; h, w even, >= 2, h w <= 2^28; dst must not be src; src and dst: any
+ * alignment (16-byte accesses are used per plane where w % 16 == 0 and that plane's address allows). */
+#define ISR_YUV_BITS 16
+#define ISR_YUV_BT601 0
+#define ISR_YUV_BT709 1
+#define ISR_YUV_I420 0
+#define ISR_YUV_NV12 1
+#define ISR_YUV_SITING_LEFT 0
+#define ISR_YUV_SITING_CENTER 1
+int isr_yuv_coeffs(int matrix, int full_range, int32_t* fwd /* [9] */, int32_t* inv /* [5] */);
+
+typedef struct isr_yuv_desc {
+    int32_t n, h, w;        /* of the RGB image = of the luma plane */
+    int32_t layout;         /* ISR_YUV_I420 / ISR_YUV_NV12 */
+    int32_t siting;         /* ISR_YUV_SITING_LEFT / ISR_YUV_SITING_CENTER */
+    int32_t full_range;     /* 0: oy = 16; non-zero: oy = 0 */
+    int32_t fwd[9], inv[5]; /* isr_yuv_coeffs' (each entry point reads its own) */
+    const uint8_t* src;
+    uint8_t* dst;
+} isr_yuv_desc;
+int isr_yuv420_to_rgb_u8(const isr_yuv_desc* d, isr_stream_t s);
+int isr_rgb_to_yuv420_u8(const isr_yuv_desc* d, isr_stream_t s);
+
 const char* isr_last_error(void);
 int isr_version(void);
 

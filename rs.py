@@ -23,6 +23,15 @@ input (.rgb, with --video_size WxH) and bgr24 output (.bgr / .raw save_dir) work
 without ffmpeg.  The per-batch forward is a captured HIP graph (video.py).
 
     python rs.py --model ck.pt --src clip.mp4 --save_dir out.mp4 --batch_size 2
+
+8-bit YUV 4:2:0 frames (half the bytes of rgb24, converted on the GPU inside the graph): a .y4m
+(YUV4MPEG2), .yuv / .i420 (headerless I420) or .nv12 source is read as such, a .y4m / .yuv / .nv12
+save_dir is written as such, both without ffmpeg; for container formats `--pix_fmt yuv420p|nv12`
+selects what is piped from and to ffmpeg.  `--yuv_matrix`, `--yuv_range`, `--yuv_siting` override
+what a .y4m header says (default: limited range, left siting, BT.709 at a height of 720 or more
+and BT.601 below, for the input and the output frame each).
+
+    python rs.py --model ck.pt --src clip.y4m --save_dir out.y4m
 """
 from __future__ import annotations
 
@@ -38,7 +47,9 @@ import torch
 from image_super_resolution_amd import checkpoint, models, tiler, video
 
 VID_FORMATS = video.VID_FORMATS
-RAW_FORMATS = (".rgb", ".raw", ".rgb24")
+RAW_FORMATS = video.RGB_FORMATS
+YUV_FORMATS = video.YUV_FORMATS
+YUV_OUT = {".y4m": "yuv420p", ".yuv": "yuv420p", ".nv12": "nv12"}  # save_dir suffix -> pix_fmt
 
 
 def read_image(path: Path) -> torch.Tensor:
@@ -82,22 +93,54 @@ def compare_with_ref(out: torch.Tensor, ref: torch.Tensor, ref_path: Path, borde
             "mse": vals[3], "mse_y": vals[4]}
 
 
+def video_formats(kw, source, result: Path):
+    """(pix_fmt_in, yuv_in, pix_fmt_out, yuv_out) of a video run.  The input's format is the source's
+    (a .y4m header's siting and range, unless a --yuv_* flag is given); the output's follows the
+    save_dir suffix, for a container --pix_fmt, and inherits the input's siting and range."""
+    flags = {k: kw.get(f"yuv_{k}") for k in ("matrix", "range", "siting")}
+
+    def with_flags(fmt: video.YUVFormat) -> video.YUVFormat:
+        return video.YUVFormat(fmt.layout, flags["matrix"] or fmt.matrix,
+                               fmt.full_range if flags["range"] is None else flags["range"] == "full",
+                               flags["siting"] or fmt.siting)
+
+    yuv_in = getattr(source, "yuv", None)
+    pix_in = "rgb24" if yuv_in is None else source.pix_fmt
+    if yuv_in is not None:
+        yuv_in = with_flags(yuv_in)
+    suffix = result.suffix.lower()
+    if suffix in (".bgr", ".raw"):
+        pix_out = "bgr24"
+    elif suffix in YUV_OUT:
+        pix_out = YUV_OUT[suffix]
+    else:
+        pix_out = "bgr24" if (kw.get("pix_fmt") or "rgb24") == "rgb24" else kw["pix_fmt"]
+    yuv_out = None
+    if pix_out != "bgr24":
+        like = yuv_in or video.YUVFormat()
+        yuv_out = with_flags(video.YUVFormat(video.yuvmod.PIX_FMTS[pix_out], "auto", like.full_range, like.siting))
+    return pix_in, yuv_in, pix_out, yuv_out
+
+
 def run_video(kw, device) -> None:
-    """rs.py:54-76: frames → HIP graph forward → BGR frames → recorder."""
+    """rs.py:54-76: frames → HIP graph forward → BGR (or 4:2:0) frames → recorder."""
     src, result = Path(kw["src"]), Path(kw["save_dir"])
     wh = kw.get("video_size")
     w, h = (int(v) for v in wh.lower().split("x")) if wh else (None, None)
-    source = video.open_video(src, w, h, kw.get("fps") or 30.0)
+    source = video.open_video(src, w, h, kw.get("fps") or 30.0, kw.get("pix_fmt") or "rgb24")
+    pix_in, yuv_in, pix_out, yuv_out = video_formats(kw, source, result)
     model = build_model(kw["model"], kw["add_rate"], kw["mean"], kw["std"])
     runner = tiler.runner_for(model, device)
     up = video.FrameUpscaler(runner.gw, source.height, source.width, kw["batch_size"], runner.mean, runner.std,
-                             device)
+                             device, pix_fmt_in=pix_in, pix_fmt_out=pix_out, yuv_in=yuv_in, yuv_out=yuv_out)
     H, W = up.out_hw
-    if result.suffix.lower() in (".bgr", ".raw"):
+    if result.suffix.lower() == ".y4m":
+        rec = video.Y4MRecorder(result, (W, H), source.fps, up.yuv_out)
+    elif result.suffix.lower() in (".bgr", ".raw", *YUV_OUT):
         rec = video.RawRecorder(result, (W, H), source.fps)
     else:
         result = result.with_suffix(".mp4")
-        rec = video.FFMPEG_recorder(result.as_posix(), (W, H), source.fps)
+        rec = video.FFMPEG_recorder(result.as_posix(), (W, H), source.fps, pix_fmt=pix_out, yuv=up.yuv_out)
     t0 = time.perf_counter()
     n = video.VideoUpscaler(up).run(source, rec)
     rec.stopRecorder()
@@ -112,7 +155,7 @@ def runer(**kw):
     if kw.get("wino") is not None:  # the default of every pack / plan below (else ISR_WINO, else off)
         from image_super_resolution_amd import engine
         engine.WINO_DEFAULT = engine.wino_mode(kw["wino"])
-    if src.suffix.lower() in VID_FORMATS + RAW_FORMATS:
+    if src.suffix.lower() in VID_FORMATS + RAW_FORMATS + YUV_FORMATS:
         if not torch.cuda.is_available():
             raise RuntimeError("rs.py runs the HIP generator and needs a GPU")
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -156,7 +199,7 @@ def runer(**kw):
         dist.destroy_process_group()
 
 
-if __name__ == "__main__":
+def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument("--model", type=str, default="")
     p.add_argument("--src", type=str, default="")
@@ -181,4 +224,18 @@ if __name__ == "__main__":
     p.add_argument("--ref", type=str, default="", help="ground-truth image of the output's size: after the still "
                    "is written, print one JSON line with its PSNR / PSNR-Y / SSIM-Y against it (image branch)")
     p.add_argument("--ref_border", type=int, default=4, help="pixels cropped from every side before the metrics")
-    runer(**vars(p.parse_args()))
+    p.add_argument("--pix_fmt", choices=("rgb24", "yuv420p", "nv12"), default="rgb24",
+                   help="video through ffmpeg: the frames piped from the decoder and to the encoder (rgb24: rgb24 in, "
+                        "bgr24 out; yuv420p / nv12: 8-bit 4:2:0 both ways, colour conversion on the GPU).  .y4m / .yuv / "
+                        ".i420 / .nv12 sources and save_dirs carry their own format")
+    p.add_argument("--yuv_matrix", choices=("auto", "bt601", "bt709"), default=None,
+                   help="4:2:0 frames: the matrix (default auto: bt709 at a height of 720 or more, else bt601)")
+    p.add_argument("--yuv_range", choices=("limited", "full"), default=None,
+                   help="4:2:0 frames: the range (default: the .y4m header's, else limited)")
+    p.add_argument("--yuv_siting", choices=("left", "center"), default=None,
+                   help="4:2:0 frames: the chroma siting (default: the .y4m header's, else left)")
+    return p
+
+
+if __name__ == "__main__":
+    runer(**vars(build_parser().parse_args()))
