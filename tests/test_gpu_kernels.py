@@ -1,9 +1,12 @@
-"""HIP kernel numerics vs a plain PyTorch fp32 reference of the same op.
+"""HIP kernel numerics vs the GPU's own fp32 F.conv2d (another vendor kernel, not a
+high-precision reference) on random normal data.
 
 Inputs and weights are rounded to bf16 first (the kernels' storage type), so
 the remaining difference is fp32 accumulation order plus one bf16 rounding of
 the output: tolerance |err| <= 1.5e-2 * max(1, |ref|) elementwise, and mean
-error < 2e-3.
+error < 2e-3 — about 7x wider than one correct rounding needs.  The stronger
+check is tests/test_gpu_exact.py: the same kernels on integer data with
+power-of-two scales must equal a float64 CPU reference rounded once.
 """
 import os
 
