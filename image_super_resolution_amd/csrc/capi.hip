@@ -29,6 +29,7 @@ int conv3x3_wino_fwd_dispatch(const isr_conv_desc* d, hipStream_t s);
 int head9x9_fwd_dispatch(const isr_head_desc* d, hipStream_t s);
 int tail9x9_fwd_dispatch(const isr_tail_desc* d, hipStream_t s);
 int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s);
+int tail_segment_rows(const isr_tail_desc* d, int cus);
 size_t head9x9_packed_bytes(int cout);
 size_t tail9x9_packed_bytes();
 int head9x9_pack(const float* w, void* out, int cout, int cin, hipStream_t s, bool h);
@@ -433,6 +434,15 @@ int isr_tail9x9_fwd_variant(const isr_tail_desc* d, int32_t variant, isr_stream_
     if (variant != 0 && variant != 3 && variant != 5)
         return fail(ISR_ERR_UNSUPPORTED, "tail9x9: variant %d " ISR_REMOVED_FORM, variant);
     return launched(isr::tail9x9_fwd_variant(d, variant, (hipStream_t)s), "tail9x9");
+}
+
+int32_t isr_tail9x9_segment_rows(const isr_tail_desc* d, int32_t cus) {
+    const int rc = tail_validate(d);
+    if (rc != ISR_OK) return rc;
+    const int sh = isr::tail_segment_rows(d, cus > 0 ? cus : isr::cu_count());
+    if (sh < 0) return fail(ISR_ERR_BAD_DESC, "tail9x9: no segment height divides ha = %d", d->ha);
+    g_err[0] = 0;
+    return sh;
 }
 
 static int wgrad_validate(const isr_wgrad_desc* d) {

@@ -528,13 +528,28 @@ int head9x9_fwd_dispatch(const isr_head_desc* d, hipStream_t s) {
     return d->f16 ? go(head9x9_kernel<true>) : go(head9x9_kernel<false>);
 }
 
+// The production choice for a descriptor on a device of `cus` compute units: the walk's segment
+// height (8 .. 512), or 0 for the per-tile fallback of images whose output passes 2 GiB (the walk
+// stores through 32-bit offsets).  -2: ha is no multiple of 8.
+// segment height: the longest walk (<= 512 rows) that still gives every CU a strip — fewer,
+// longer walks recompute fewer halo T rows and leave no partial last wave of blocks:
+// 16x512^2 fp32 179 us at 128 rows, 164 at 256, 157 at 512 (profiles/r02_tail_sh.jsonl)
+int tail_segment_rows(const isr_tail_desc* d, int cus) {
+    if ((size_t)3 * d->h * d->w * (d->y_u8 ? 1 : 4) >= ((size_t)1 << 31)) return 0;
+    int sh = 512;
+    while (sh > 8 && (d->ha % sh || (long)d->n * (d->wa / tail8w::TW) * (d->ha / sh) < cus)) sh >>= 1;
+    while (d->ha % sh) sh >>= 1;
+    return sh < 8 ? -2 : sh;
+}
+
 // variant 0 = production = 5, the 8-wave row-streaming walk (170-177 us at 16 x 512^2, fp32 out,
 // against 354-375 us for the 8-row per-tile kernel, variant 3); 3 is also the fallback of images
-// whose output passes 2 GiB (the walk stores through 32-bit offsets).  -2: any other id.
+// whose output passes 2 GiB.  -2: any other id.
 int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s) {
     if (variant == 0) variant = 5;
     if (variant != 3 && variant != 5) return -2;
-    if (variant == 5 && (size_t)3 * d->h * d->w * (d->y_u8 ? 1 : 4) >= ((size_t)1 << 31)) variant = 3;
+    const int sh = variant == 5 ? tail_segment_rows(d, cu_count()) : 0;
+    if (sh == 0) variant = 3;
     if (variant == 3) {
         auto go = [&](auto kern) {
             lds_limit((const void*)kern, tail8::LDS);
@@ -543,12 +558,6 @@ int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s) {
         };
         return d->f16 ? go(tail9x9_k8_kernel<true>) : go(tail9x9_k8_kernel<false>);
     }
-    // segment height: the longest walk (<= 512 rows) that still gives every CU a strip — fewer,
-    // longer walks recompute fewer halo T rows and leave no partial last wave of blocks:
-    // 16x512^2 fp32 179 us at 128 rows, 164 at 256, 157 at 512 (profiles/r02_tail_sh.jsonl)
-    int sh = 512;
-    while (sh > 8 && (d->ha % sh || (long)d->n * (d->wa / tail8w::TW) * (d->ha / sh) < cu_count())) sh >>= 1;
-    while (d->ha % sh) sh >>= 1;
     if (sh < 8) return -2;
     const int blocks = d->n * (d->wa / tail8w::TW) * (d->ha / sh);
     auto go = [&](auto kern) {

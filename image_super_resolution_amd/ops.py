@@ -358,6 +358,15 @@ def launch_tail9x9(d: IsrTailDesc) -> None:
     check(_lib.load().isr_tail9x9_fwd(ctypes.byref(d), _stream()), "isr_tail9x9_fwd")
 
 
+def tail9x9_segment_rows(d: IsrTailDesc, cus: int = 0) -> int:
+    """The segment height isr_tail9x9_fwd walks for `d` on `cus` compute units (0: this device's);
+    0 when it takes the per-tile kernel (an image's output reaches 2 GiB).  Nothing is launched."""
+    sh = _lib.load().isr_tail9x9_segment_rows(ctypes.byref(d), cus)
+    if sh < 0:
+        check(sh, "isr_tail9x9_segment_rows")
+    return sh
+
+
 def tail9x9(x: ActBuffer, wpack: torch.Tensor, bias: torch.Tensor | None, out: torch.Tensor) -> None:
     """out (NCHW [n,3,h,w], fp32 or uint8) = tanh(conv9x9(x) + bias) (→ uint8 image)."""
     launch_tail9x9(tail9x9_desc(x, wpack, bias, out))

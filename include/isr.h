@@ -459,6 +459,13 @@ int isr_tail9x9_fwd(const isr_tail_desc* d, isr_stream_t s);
  * forms that measured slower) returns ISR_ERR_UNSUPPORTED in every build; DESIGN.md section 5
  * keeps their history.  Same descriptor rules as isr_tail9x9_fwd. */
 int isr_tail9x9_fwd_variant(const isr_tail_desc* d, int32_t variant, isr_stream_t s);
+/* What isr_tail9x9_fwd would run for `d` on a device of `cus` compute units (cus <= 0: the current
+ * device's): the walk's segment height in rows, 8 .. 512, a power of two — 512 halved while it does
+ * not divide ha or while n * (wa / 32) * (ha / rows) < cus — or 0 when the per-tile kernel is taken
+ * because the output of one image reaches 2 GiB (3 * h * w * element size >= 2^31).  Same descriptor
+ * rules as isr_tail9x9_fwd: a negative ISR_ERR_* with isr_last_error() set on a bad descriptor.
+ * Launches nothing and follows no pointer of the descriptor. */
+int32_t isr_tail9x9_segment_rows(const isr_tail_desc* d, int32_t cus);
 
 /* ---- multi-tensor optimiser ops (one launch over every parameter) ---------
  * A tensor is n fp32 elements at each non-null pointer (same element order);

@@ -1,6 +1,7 @@
 """Float64 CPU references for the exact-arithmetic tests of the MFMA conv, dgrad and wgrad kernels
 (tests/test_gpu_exact.py), their integer input generators, and the table of cases both that file and
-tests/test_exact_ref_cpu.py walk.  No HIP, no GPU.
+tests/test_exact_ref_cpu.py walk; at the end, the same for the 9x9 tail forward
+(tests/test_gpu_tail_exact.py, tests/test_tail_exact_cpu.py).  No HIP, no GPU.
 
 Why equality is a fair demand: activations, gradients and weights are small integers, the bias is
 k/64 (k/1024 for the 9x9 head, whose sums are too small to round in fp16 otherwise) and every
@@ -388,3 +389,131 @@ def tail_dgrad_inputs(grid):
     ref = torch.where(m > 0, gu, gu * MSLOPE)
     assert_fp32_exact(ref)
     return W2, gp, m, ref
+
+
+# ------------------------------------------------------------------ the 9x9 tail forward (conv2 + tanh)
+# Activations are integers in [-3, 3], weights k/256 with |k| <= 2, the bias k/256 with |k| <= 64: all
+# exact in bf16 and fp16, every partial sum a multiple of 1/256 of magnitude <= 31168/256, so the
+# pre-activation s is exact in fp32 in any summation order and lies on the grid of step 1/256.  tanhf is
+# not correctly rounded, so the fp32 output is not pinned to a bit pattern but to a bracket: with
+# hstep = 1/512 (half a grid step) the output must lie strictly inside
+# (tanh64(s - hstep), tanh64(s + hstep)).  Any tanhf good to a few ulps passes (the narrower side is
+# 43.85 fp32 ulps at |s| = 4, more below); an output computed from any other grid point fails, and a wrong
+# tap, row, channel, ring slot or image moves s by whole grid steps.  Past |s| = 4 the bracket narrows
+# below what a tanhf owes, so there only the sign and tanh64(4 - hstep) <= |out| <= 1 are demanded, and
+# a case may have at most 0.1 % of such pixels.
+TAIL_GRID = 256
+TAIL_HSTEP = 1.0 / 512
+TAIL_SMAX = 4.0
+TAIL_FAR_SHARE = 1e-3
+TAIL_SH = (8, 16, 32, 64, 128, 256, 512)
+
+
+def tail_weights(g):
+    """[3, 64, 9, 9] of k/256, integer k in [-2, 2]."""
+    return weights((3, 64, 9, 9), g) / TAIL_GRID
+
+
+def tail_bias(g):
+    """[3] of k/256, integer |k| <= 64."""
+    return _ints((3,), -64, 64, g) / TAIL_GRID
+
+
+def tail_preact(xp, W, b=None) -> torch.Tensor:
+    """s = conv9x9(x) + bias in float64.  xp [n, 64, h + 8, w + 8] carries its own zero halo of 4 (as the
+    activation buffer does), so a column slice [x0 - 4, x0 + 36) of a wide image gives that strip alone."""
+    # the generators' ranges, from which the sum bound follows for any data (|s| <= 31168/256 < 2^24/256:
+    # assert_sum_bound on the all-extreme tensors, tests/test_tail_exact_cpu.py)
+    for t, lim, gran in ((xp, 3, 1), (W, 2, TAIL_GRID), (b, 64, TAIL_GRID)):
+        if t is not None:
+            assert t.dtype == F64 and torch.equal(t * gran, (t * gran).round()) and (t * gran).abs().max().item() <= lim
+    s = F.conv2d(xp, W, None)
+    if b is not None:
+        s = s + b.view(1, -1, 1, 1)
+    assert_fp32_exact(s, "pre-activation")
+    assert torch.equal(s * TAIL_GRID, (s * TAIL_GRID).round()), "pre-activation off the 1/256 grid"
+    return s
+
+
+def fp32_ulp(v: torch.Tensor) -> torch.Tensor:
+    """The fp32 spacing at |v| (float64 in and out; the smallest normal's below it)."""
+    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
+    return torch.exp2(e - 23)
+
+
+def tail_bracket_ulps(s: torch.Tensor) -> torch.Tensor:
+    """Per element of s with |s| <= 4: the smaller distance from tanh64(s) to the bracket's ends, in
+    fp32 ulps of tanh64(s)."""
+    t = torch.tanh(s)
+    room = torch.minimum(torch.tanh(s + TAIL_HSTEP) - t, t - torch.tanh(s - TAIL_HSTEP))
+    return (room / fp32_ulp(t))[s.abs() <= TAIL_SMAX]
+
+
+def check_tail_fp32(out: torch.Tensor, s: torch.Tensor, what: str = "tail") -> dict:
+    """The fp32 bar of the tail: `out` (fp32, the kernel's) against the float64 pre-activation `s` of the
+    same pixels.  Returns what it saw: pixels, share past |s| = 4, distinct s, exact zeros of s, and the
+    largest |out - tanh64(s)| in fp32 ulps (informative: tanhf's own error)."""
+    assert out.dtype == torch.float32 and out.shape == s.shape and s.dtype == F64, (out.dtype, out.shape, s.shape)
+    o, s = out.double().flatten(), s.flatten()
+    far = s.abs() > TAIL_SMAX
+    share = far.double().mean().item()
+    assert share <= TAIL_FAR_SHARE, f"{what}: {share:.4%} of the pixels have |s| > {TAIL_SMAX}"
+    near = ~far
+    lo, hi = torch.tanh(s - TAIL_HSTEP), torch.tanh(s + TAIL_HSTEP)
+    bad = near & ~((o > lo) & (o < hi))
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {s.numel()} outputs outside their bracket, first at flat "
+                             f"index {i}: s = {s[i].item()!r}, got {o[i].item()!r}, bracket ({lo[i].item()!r}, "
+                             f"{hi[i].item()!r})")
+    floor = torch.tanh(torch.tensor(TAIL_SMAX - TAIL_HSTEP, dtype=F64)).item()
+    ok_far = (torch.sign(o) == torch.sign(s)) & (o.abs() >= floor) & (o.abs() <= 1.0)
+    assert bool(ok_far[far].all()), f"{what}: a saturated output has the wrong sign or magnitude"
+    # the output is a function of s: equal s, equal bits
+    key = (s * TAIL_GRID).round().to(torch.int64)
+    bits = out.flatten().contiguous().view(torch.int32).to(torch.int64)
+    order = torch.argsort(key, stable=True)
+    k, v = key[order], bits[order]
+    twin = k[1:] == k[:-1]
+    assert bool((v[1:][twin] == v[:-1][twin]).all()), f"{what}: equal pre-activations gave different output bits"
+    t = torch.tanh(s)
+    return dict(pixels=s.numel(), far=share, distinct=int(torch.unique(key).numel()), zeros=int((key == 0).sum()),
+                tanhf_ulps=((o - t).abs() / fp32_ulp(t))[near].max().item())
+
+
+def tail_u8_expected(t: torch.Tensor) -> torch.Tensor:
+    """The uint8 image of the kernel's own fp32 output t, in fp32 on the CPU with the kernel's operations:
+    clamp(round_half_even(((t + 1) / 2) * 255), 0, 255)."""
+    assert t.dtype == torch.float32 and t.device.type == "cpu"
+    return torch.clamp(torch.round(((t + 1) / 2) * 255), 0, 255).to(torch.uint8)
+
+
+def tail_segment_rule(n, h, w, u8, cus, ha=None, wa=None) -> int:
+    """The tail dispatcher's rule, restated: 0 = the per-tile kernel (an image's output reaches 2 GiB),
+    else the walk's segment height: 512 halved while it does not divide ha or leaves a CU without a block."""
+    if 3 * h * w * (1 if u8 else 4) >= 2 ** 31:
+        return 0
+    ha = -(-h // 32) * 32 if ha is None else ha
+    wa = -(-w // 32) * 32 if wa is None else wa
+    sh = 512
+    while sh > 8 and (ha % sh or n * (wa // 32) * (ha // sh) < cus):
+        sh //= 2
+    return sh
+
+
+def tail_case(sh, m, cus, strips):
+    """(n, h, w) on which a device of `cus` compute units walks segments of `sh` rows.  The computed height
+    is ha = m * max(sh, 32), m in {1, 3} (computed regions are multiples of 32 rows): from 32 rows on no
+    larger power of two divides ha, and the batch gives n * strips * (ha / sh) >= cus blocks; below 32 the
+    block count alone decides, so the batch is the smallest that fills the CUs at sh (sh = 16), or a small
+    one that cannot fill them at 16 (sh = 8).  h = ha - 5 (h % 16 = 11: a partial last tile and rows the
+    walk computes but must not store), w = 32 * strips - 9 (a last strip of 23 columns)."""
+    assert sh in TAIL_SH and m in (1, 3)
+    ha = m * max(sh, 32)
+    nseg = ha // sh
+    need = -(-cus // nseg)                      # n * strips >= ceil(cus / nseg)
+    n = 2 if sh == 8 else max(2, -(-need // strips))
+    h, w = ha - 5, 32 * strips - 9
+    for u8 in (False, True):
+        assert tail_segment_rule(n, h, w, u8, cus) == sh, (sh, m, cus, strips, n)
+    return n, h, w

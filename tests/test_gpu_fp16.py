@@ -136,7 +136,8 @@ def test_head9x9_f16(u8):
 @pytest.mark.parametrize("n,h,w", [(2, 40, 72), (3, 96, 64)])
 def test_tail9x9_f16_stream_vs_per_tile_and_ref(n, h, w):
     """The production row-streaming tail (variant 5) and its large-image fallback (3) in fp16: bit
-    for bit the same sums, and within the fp16 bar of the fp32 reference."""
+    for bit the same sums, and within the fp16 bar of the fp32 reference.  Both shapes walk segments
+    of 8 rows on 256 CUs (asserted); the longer walks are tests/test_gpu_tail_exact.py's."""
     from image_super_resolution_amd import _lib, ops
     lib = _lib.load()
     x = _mk(n, 64, h, w, 21) * 0.5
@@ -148,7 +149,7 @@ def test_tail9x9_f16_stream_vs_per_tile_and_ref(n, h, w):
     def run(v, dt):
         o = torch.full((n, 3, h, w), 7, device=DEV, dtype=dt)
         d = ops.tail9x9_desc(xb, wp, b, o)
-        assert d.f16 == 1
+        assert d.f16 == 1 and ops.tail9x9_segment_rows(d) == 8, ops.tail9x9_segment_rows(d)
         ops.check(lib.isr_tail9x9_fwd_variant(ctypes.byref(d), v, ops._stream()), f"tail variant {v}")
         torch.cuda.synchronize()
         return o

@@ -171,9 +171,11 @@ def test_tail9x9(u8):
 
 @pytest.mark.parametrize("n,h,w", [(2, 40, 72), (5, 128, 160), (3, 96, 64), (2, 300, 96)])
 def test_tail9x9_persistent_vs_per_tile(n, h, w):
-    """The production row-streaming tail (variant 5, 8 waves; segment heights 16 / 128 / 32 / 16
-    here) vs the 8-row per-tile kernel (variant 3, its large-image fallback): the same sums in the
-    same order, so bit-identical, and run-to-run bit equality."""
+    """The production row-streaming tail (variant 5, 8 waves) vs the 8-row per-tile kernel (variant 3,
+    its large-image fallback): the same sums in the same order, so bit-identical, and run-to-run bit
+    equality.  None of these shapes gives every one of the 256 CUs a block at 16 rows, so all four walk
+    segments of 8 rows (two iterations: no ring wrap, no steady state), which is asserted; the longer
+    walks are tests/test_gpu_tail_exact.py's."""
     import ctypes
     from image_super_resolution_amd import ops, _lib
     lib = _lib.load()
@@ -187,6 +189,7 @@ def test_tail9x9_persistent_vs_per_tile(n, h, w):
         o = torch.empty(n, 3, h, w, device=DEV, dtype=dt) if fill is None else \
             torch.full((n, 3, h, w), fill, device=DEV, dtype=dt)
         d = ops.tail9x9_desc(xb, wp, b, o)
+        assert ops.tail9x9_segment_rows(d) == 8, ops.tail9x9_segment_rows(d)
         ops.check(lib.isr_tail9x9_fwd_variant(ctypes.byref(d), v, ops._stream()), f"tail variant {v}")
         torch.cuda.synchronize()
         return o
