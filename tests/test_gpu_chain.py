@@ -9,9 +9,9 @@ import torch
 
 from image_super_resolution_amd import engine, models
 from image_super_resolution_amd.weights import normalize, synth_lr_batch, synth_state_dict
+from trunk_harness import DEV, MEAN, STD, lr_inputs, pack, run_plan
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 # Both libraries carry one trunk form (variant 0); with ISR_LIB=.../libisr_tuning.so this file runs
 # the instrumented build of the same kernel.
 
@@ -19,41 +19,6 @@ DEV = "cuda"
 @pytest.fixture(scope="module", autouse=True)
 def lib(built_lib):
     return built_lib
-
-
-def _gw(blocks, scale=4, enchant=False, seed=0, f16=True):
-    m = (models.EResNet if enchant else models.ResNet)(blocks, 0.2, scaleRate=scale)
-    sd = synth_state_dict(m.state_dict(), seed)
-    return engine.pack_generator({k: v.to(DEV) for k, v in sd.items()}, enchant=enchant, device=DEV, f16=f16)
-
-
-def _run(gw, xs, chain, acquire=False, variant=0):
-    """One plan, one forward per input in `xs` (different inputs back to back: a stale
-    hand-off read would return the previous input's activations and show up)."""
-    x0 = xs[0]
-    old = engine.CHAIN_VARIANT
-    engine.CHAIN_VARIANT = variant
-    try:
-        plan = engine.GeneratorPlan(gw, x0.shape[0], x0.shape[2], x0.shape[3], x0.device, False, False,
-                                    (0.485, 0.456, 0.406), (0.229, 0.224, 0.225), chain=chain,
-                                    chain_acquire=acquire)
-    finally:
-        engine.CHAIN_VARIANT = old
-    if chain:
-        assert plan.chain is not None and plan.chain.variant == variant
-    outs = []
-    for x in xs:
-        out = torch.empty(plan.out_shape, device=DEV)
-        plan.run(x, out)
-        outs.append(out)
-    torch.cuda.synchronize()
-    if chain:
-        assert plan.chain is not None and not plan.chain.failed(), "a chain dependency wait gave up"
-    return outs
-
-
-def _inputs(n, h, w, k, seed):
-    return [normalize(synth_lr_batch(n, h, w, seed=seed + i, scale=4)[0]).to(DEV).contiguous() for i in range(k)]
 
 
 # (4, 512, 512) = 2,048 tiles and (1, 540, 960) = 1,020 ragged tiles: more tiles than the 512
@@ -66,25 +31,26 @@ def _inputs(n, h, w, k, seed):
 @pytest.mark.parametrize("f16", [True, False], ids=["fp16", "bf16"])
 def test_chain_bitwise_equals_per_conv_launches(n, h, w, blocks, f16):
     """fp16 storage (the inference default) and bf16 (the training forward's storage)."""
-    gw = _gw(blocks, f16=f16)
-    xs = _inputs(n, h, w, 3, seed=3)
-    refs = _run(gw, xs, chain=False)
-    variant = 0
+    # not harness.model_case: the references of the large geometries (3.4 GB at 10 x 768 x 768) are
+    # not worth holding for the session
+    gw = pack(blocks, f16=f16)
+    xs = lr_inputs(n, h, w, 3, seed=3)
+    refs = run_plan(gw, xs, chain=False)[0]
     for acquire in (False, True):
-        for out, ref in zip(_run(gw, xs, chain=True, acquire=acquire, variant=variant), refs):
+        for out, ref in zip(run_plan(gw, xs, chain=True, acquire=acquire)[0], refs):
             assert torch.equal(out, ref), \
-                f"chain variant {variant} (acquire={acquire}) differs: max {(out - ref).abs().max().item()}"
+                f"chain variant 0 (acquire={acquire}) differs: max {(out - ref).abs().max().item()}"
 
 
 def test_chain_repeated_stress_eresnet():
     """EResNet (no BN; conv weights scaled 0.2): 20 back-to-back chained forwards at the
     bench shape over 4 different inputs in turn, every output bitwise equal to the
     per-conv launches of the same input."""
-    gw = _gw(4, enchant=True, seed=2)
-    xs = _inputs(16, 128, 128, 4, seed=9)
-    refs = _run(gw, xs, chain=False)
+    gw = pack(4, enchant=True, seed=2)
+    xs = lr_inputs(16, 128, 128, 4, seed=9)
+    refs = run_plan(gw, xs, chain=False)[0]
     for _ in range(5):
-        for out, ref in zip(_run(gw, xs, chain=True), refs):
+        for out, ref in zip(run_plan(gw, xs, chain=True)[0], refs):
             assert torch.equal(out, ref)
 
 
@@ -92,10 +58,9 @@ def test_chain_rejects_a_bad_layer_table_loudly():
     """The trunk kernel's prep pass refuses a layer table its records cannot express (here: a
     growth layer whose kind says 'final'): the launch gives up (state[1] == state[0]) instead of
     computing garbage silently, and the product-path check raises."""
-    gw = _gw(1)
-    x = _inputs(2, 32, 32, 1, seed=1)[0]
-    plan = engine.GeneratorPlan(gw, 2, 32, 32, x.device, False, False, (0.485, 0.456, 0.406),
-                                (0.229, 0.224, 0.225), chain=True)
+    gw = pack(1)
+    x = lr_inputs(2, 32, 32, 1, seed=1)[0]
+    plan = engine.GeneratorPlan(gw, 2, 32, 32, x.device, False, False, MEAN, STD, chain=True)
     assert plan.chain.variant == 0
     plan.chain._kinds[0] = 1  # growth conv (cout 32) declared as an RDB final conv
     out = torch.empty(plan.out_shape, device=DEV)
@@ -141,7 +106,7 @@ def test_give_up_raises_from_video_and_tiler_before_output():
     call and the tiler's canvas."""
     import numpy as np
     from image_super_resolution_amd import tiler, video
-    gw = _gw(1, scale=2)
+    gw = pack(1, scale=2)
     up = video.FrameUpscaler(gw, 24, 40, batch=2)
     assert up.plan.chains, "the video plan must run the trunk on the persistent chain"
     frames = [np.full((24, 40, 3), i, np.uint8) for i in range(5)]
@@ -155,7 +120,7 @@ def test_give_up_raises_from_video_and_tiler_before_output():
     up.plan.chain.state[2] += 1
     with pytest.raises(engine.ChainFailed):
         up(torch.from_numpy(np.stack(frames[:2])))
-    runner = tiler.GeneratorRunner(gw, (0.485, 0.456, 0.406), (0.229, 0.224, 0.225), DEV)
+    runner = tiler.GeneratorRunner(gw, MEAN, STD, DEV)
     tu = tiler.TileUpscaler(runner, scale=2, window=32, halo=0, batch=4)
     img = torch.randint(0, 255, (3, 40, 70), dtype=torch.uint8)
     tu(img)

@@ -16,18 +16,12 @@ hipcc canonicalises both inputs of a max with one more v_max each, so the max fo
 2.5 instructions per value (with the packed multiply) and would add a -0 / NaN argument for nothing.
 The zeros stay as a probe of that choice; fp32 accumulators of real convolutions seldom land on
 +-0, so they show little by themselves."""
-import ctypes
-import functools
-
 import pytest
 import torch
 
-from image_super_resolution_amd import engine, models, ops
-from image_super_resolution_amd.weights import normalize, synth_lr_batch, synth_state_dict
+import trunk_harness as H
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -35,96 +29,33 @@ def lib(built_lib):
     return built_lib
 
 
-def _inputs(n, h, w, k, seed):
-    xs = []
-    for i in range(k):
-        x = normalize(synth_lr_batch(n, h, w, seed=seed + i, scale=4)[0])
-        x[..., ::7] = 0
-        xs.append(x.to(DEV).contiguous())
-    return xs
-
-
-def _run(gw, xs, chain):
-    x0 = xs[0]
-    plan = engine.GeneratorPlan(gw, x0.shape[0], x0.shape[2], x0.shape[3], x0.device, False, False, MEAN, STD,
-                                chain=chain, chain_acquire=False)
-    assert (plan.chain is not None) == chain
-    outs = []
-    for x in xs:
-        out = torch.empty(plan.out_shape, device=DEV)
-        plan.run(x, out)
-        outs.append(out)
-    torch.cuda.synchronize()
-    if chain:
-        assert plan.chain.variant == 0 and not plan.chain.failed(), "a chain dependency wait gave up"
-    return outs
-
-
-@functools.lru_cache(maxsize=None)
-def _model_case(n, h, w, blocks, f16):
-    """Weights, inputs and the per-conv reference outputs of one geometry (computed once)."""
-    m = models.ResNet(blocks, 0.2, scaleRate=4)
-    sd = synth_state_dict(m.state_dict(), 0)
-    gw = engine.pack_generator({k: v.to(DEV) for k, v in sd.items()}, enchant=False, device=DEV, f16=f16)
-    xs = _inputs(n, h, w, 3, seed=11)
-    return gw, xs, _run(gw, xs, chain=False)
-
-
 @pytest.mark.parametrize("f16", [True, False], ids=["fp16", "bf16"])
 @pytest.mark.parametrize("n,h,w,blocks", [(1, 16, 32, 1), (1, 32, 64, 1), (2, 36, 52, 2), (1, 20, 40, 1)],
                          ids=["one_full_tile", "four_full_tiles", "ragged_beside_full", "all_ragged"])
 def test_epilogue_forms_bitwise_equal_per_conv_launches(n, h, w, blocks, f16):
-    gw, xs, refs = _model_case(n, h, w, blocks, f16)
-    for out, ref in zip(_run(gw, xs, chain=True), refs):
+    gw, xs, refs = H.model_case(n, h, w, blocks, f16, 11, zero_every=7)
+    for out, ref in zip(H.run_plan(gw, xs, chain=True)[0], refs):
         assert torch.equal(out, ref), f"chain differs from the per-conv launches: max {(out - ref).abs().max().item()}"
 
 
 # ---- the fallback: a growth-only chain (80 -> 32 at channel 80, 112 -> 32 at 112, 144 -> 32 at 144
 # over one 192-channel buffer) whose LeakyReLU slope is inside or outside (0, 1) ----
-GROWTH_LAYERS = ((80, 80), (112, 112), (144, 144))
+GROWTH_LAYERS = ((80, 80), (112, 112), (144, 144))  # (cin, y_coff)
 
 
-@functools.lru_cache(maxsize=None)
-def _slope_case(n, h, w, f16, slope):
-    dtype = torch.float16 if f16 else torch.bfloat16
-    g = torch.Generator().manual_seed(5)
-    buf = ops.ActBuffer.alloc(n, h, w, 192, 1, DEV, dtype=dtype)
-    keep, descs = [], []
-    for cin, coff in GROWTH_LAYERS:
-        wt = (torch.randn(32, cin, 3, 3, generator=g) * (1.5 / (9 * cin) ** 0.5)).to(DEV)
-        b = (torch.randn(32, generator=g) * 0.1).to(DEV).contiguous()
-        wp = ops.pack_conv3x3(wt, f16=f16)
-        keep += [wp, b]
-        descs.append(ops.conv3x3_desc(buf, cin, wp, b, 32, buf, y_coff=coff, slope=slope))
-    xs = []
-    for i in range(3):
-        x = torch.randn(n, 80, h, w, generator=torch.Generator().manual_seed(20 + i))  # both signs
-        x[..., ::7] = 0
-        xs.append(x.to(DEV))
-    refs = []
-    for x in xs:
-        buf.t.zero_()
-        buf.set_nchw(x, 0)
-        for d in descs:
-            ops.launch_conv3x3(d)
-        torch.cuda.synchronize()
-        refs.append(buf.t.clone())
-    return buf, descs, xs, refs, keep
+def slope_case(slope):
+    """Standard-normal inputs (both signs) with every seventh column zero."""
+    layers = tuple(H.growth(cin, coff, slope) for cin, coff in GROWTH_LAYERS)
+    return H.ChainCase(layers, in_ch=(80,), wseed=5, xseeds=((20,), (21,), (22,)), zero_every=7)
+
+
+SLOPES = (0.2, 1.0, 1.5)
 
 
 @pytest.mark.parametrize("f16", [True, False], ids=["fp16", "bf16"])
-@pytest.mark.parametrize("slope", [0.2, 1.0, 1.5], ids=["slope0.2", "slope1.0", "slope1.5"])
+@pytest.mark.parametrize("slope", SLOPES, ids=["slope0.2", "slope1.0", "slope1.5"])
 def test_growth_chain_slopes_inside_and_outside_unit_interval(slope, f16):
-    buf, descs, xs, refs, _ = _slope_case(2, 36, 52, f16, slope)
-    chain = engine.ConvChain(descs, buf, DEV, acquire=False, variant=0)
-    stream = ops._stream()
-    for x, ref in zip(xs, refs):
-        buf.t.zero_()
-        buf.set_nchw(x, 0)
-        ops.check(chain.fn(ctypes.byref(chain.desc), stream), "isr_conv_chain")
-        torch.cuda.synchronize()
-        assert not chain.failed(), "a chain dependency wait gave up"
-        assert torch.equal(buf.t, ref), \
-            f"chain differs from the per-conv launches: max {(buf.t.float() - ref.float()).abs().max().item()}"
+    built = H.chain_case(slope_case(slope), 2, 36, 52, f16)
+    H.check_chain(built, 0, acquire=False)
     # the layers' outputs (planes 5..10 of [n][c/16][hp][wp][16]) hold negative values: the slope acted
-    assert (refs[0][:, 80 // 16:].float() < 0).any(), "the case needs negative pre-activations"
+    assert (built.refs[0][0][:, 80 // 16:].float() < 0).any(), "the case needs negative pre-activations"

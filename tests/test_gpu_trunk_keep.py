@@ -14,28 +14,15 @@ final conv followed by a pair checks that form alone, and that a pair reading fr
 channels into the final conv's output, whose chunks are other planes, keeps nothing.  The switch
 ISR_TRUNK_KEEP is read once per process, so each value runs in a child process (this file's
 __main__): under 0, 1 and 2 the chain must equal the per-conv result."""
-import ctypes
-import functools
 import json
 import os
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parents[1]
-if __name__ == "__main__":
-    sys.path.insert(0, str(ROOT))
-
-from image_super_resolution_amd import engine, models, ops  # noqa: E402
-from image_super_resolution_amd.weights import normalize, synth_lr_batch, synth_state_dict  # noqa: E402
+import trunk_harness as H
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-TILE_H, TILE_W = 16, 32
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -43,104 +30,35 @@ def lib(built_lib):
     return built_lib
 
 
-def paired_layers(chain):
-    """Geometry word r0 of the chain's last launch (trunk_common.h trunk_rec_off): kept tiles exist
-    only where layers were paired."""
-    d = chain.desc
-    ntiles = d.n * (d.ha // TILE_H) * (d.wa // TILE_W)
-    rec_off = (ntiles + 4 + 15) // 16 * 16 + 16
-    return int(chain.state[rec_off - 16 + 13].item())
-
-
 # ---------------------------------------------------------------- whole generators
-def _run(gw, xs, chain, acquire=False):
-    x0 = xs[0]
-    plan = engine.GeneratorPlan(gw, x0.shape[0], x0.shape[2], x0.shape[3], x0.device, False, False, MEAN, STD,
-                                chain=chain, chain_acquire=acquire)
-    assert (plan.chain is not None) == chain
-    outs = []
-    for x in xs:
-        out = torch.empty(plan.out_shape, device=DEV)
-        plan.run(x, out)
-        outs.append(out)
-    torch.cuda.synchronize()
-    if chain:
-        assert plan.chain.variant == 0 and not plan.chain.failed(), "a chain dependency wait gave up"
-    return outs, (paired_layers(plan.chain) if chain else None)
-
-
-@functools.lru_cache(maxsize=None)
-def _model_case(n, h, w, blocks, f16):
-    m = models.ResNet(blocks, 0.2, scaleRate=4)
-    sd = synth_state_dict(m.state_dict(), 0)
-    gw = engine.pack_generator({k: v.to(DEV) for k, v in sd.items()}, enchant=False, device=DEV, f16=f16)
-    xs = [normalize(synth_lr_batch(n, h, w, seed=11 + i, scale=4)[0]).to(DEV).contiguous() for i in range(3)]
-    return gw, xs, _run(gw, xs, chain=False)[0]
-
-
+# (the geometry word r0: kept tiles exist only where layers were paired)
 @pytest.mark.parametrize("acquire", [False, True], ids=["plain", "acquire"])
 @pytest.mark.parametrize("f16", [True, False], ids=["fp16", "bf16"])
 @pytest.mark.parametrize("n,h,w,blocks", [(1, 16, 32, 1), (1, 48, 96, 1), (2, 36, 52, 2), (3, 224, 416, 1)],
                          ids=["one_tile", "3x3_tiles", "ragged", "546_tiles"])
 def test_generator_kept_tiles_bitwise_equal_per_conv_launches(n, h, w, blocks, f16, acquire):
-    gw, xs, refs = _model_case(n, h, w, blocks, f16)
-    outs, r0 = _run(gw, xs, chain=True, acquire=acquire)
+    gw, xs, refs = H.model_case(n, h, w, blocks, f16, 11)
+    outs, r0 = H.run_plan(gw, xs, chain=True, acquire=acquire)
     assert r0 == 4 * 3 * blocks, f"paired layers {r0}: every RDB has two growth pairs, each with a kept hand-off"
     for out, ref in zip(outs, refs):
         assert torch.equal(out, ref), f"chain differs from the per-conv launches: max {(out - ref).abs().max().item()}"
 
 
 # ---------------------------------------------------------------- hand-built growth-only chains
-# a layer: (cin, y_coff, slope); every layer reads channels [0, cin) of one 192-channel buffer and
-# writes 32 channels at y_coff of the same buffer
-RDB4 = ((64, 64, 0.2), (96, 96, 0.35), (128, 128, 0.5), (160, 160, 0.65))
+# every layer reads channels [0, cin) of one 192-channel buffer and writes 32 channels at y_coff of
+# the same buffer: H.growth(cin, y_coff, slope)
+RDB4 = (H.growth(64, 64, 0.2), H.growth(96, 96, 0.35), H.growth(128, 128, 0.5), H.growth(160, 160, 0.65))
+XSEEDS = ((40,), (41,), (42,))  # [input][buffer]
 CHAINS = {
-    # name: (layers, expected paired layers)
-    "rdb4_slopes": (RDB4, 4),
-    "pair_then_single": (RDB4[:3], 2),
+    # name: (case, expected paired layers)
+    "rdb4_slopes": (H.ChainCase(RDB4, in_ch=(64,), wseed=9, xseeds=XSEEDS), 4),
+    "pair_then_single": (H.ChainCase(RDB4[:3], in_ch=(64,), wseed=9, xseeds=XSEEDS), 2),
 }
 
 
-@functools.lru_cache(maxsize=None)
-def _chain_case(name, n, h, w, f16):
-    """The buffer, descriptors, three inputs and the buffer contents the per-conv launches leave for
-    each input."""
-    layers, want = CHAINS[name]
-    dtype = torch.float16 if f16 else torch.bfloat16
-    g = torch.Generator().manual_seed(9)
-    buf = ops.ActBuffer.alloc(n, h, w, 192, 1, DEV, dtype=dtype)
-    hold, descs = [], []
-    for cin, coff, slope in layers:
-        wt = (torch.randn(32, cin, 3, 3, generator=g) * (1.5 / (9 * cin) ** 0.5)).to(DEV)
-        b = (torch.randn(32, generator=g) * 0.1).to(DEV).contiguous()
-        wp = ops.pack_conv3x3(wt, f16=f16)
-        hold += [wp, b]
-        descs.append(ops.conv3x3_desc(buf, cin, wp, b, 32, buf, y_coff=coff, slope=slope))
-    xs = [torch.randn(n, 64, h, w, generator=torch.Generator().manual_seed(40 + i)).to(DEV) for i in range(3)]
-    refs = []
-    for x in xs:
-        buf.t.zero_()
-        buf.set_nchw(x, 0)
-        for d in descs:
-            ops.launch_conv3x3(d)
-        torch.cuda.synchronize()
-        refs.append(buf.t.clone())
-    return buf, descs, xs, refs, want, hold
-
-
 def _check_chain(name, n, h, w, f16, acquire):
-    buf, descs, xs, refs, want, _ = _chain_case(name, n, h, w, f16)
-    chain = engine.ConvChain(descs, buf, DEV, acquire=acquire, variant=0)
-    stream = ops._stream()
-    for x, ref in zip(xs, refs):
-        buf.t.zero_()
-        buf.set_nchw(x, 0)
-        ops.check(chain.fn(ctypes.byref(chain.desc), stream), "isr_conv_chain")
-        torch.cuda.synchronize()
-        assert not chain.failed(), "a chain dependency wait gave up"
-        assert torch.equal(buf.t, ref), \
-            f"chain differs from the per-conv launches: max {(buf.t.float() - ref.float()).abs().max().item()}"
-    r0 = paired_layers(chain)
+    case, want = CHAINS[name]
+    r0 = H.check_chain(H.chain_case(case, n, h, w, f16), 0, acquire)
     assert r0 == want, f"paired layers {r0}"
     return r0
 
@@ -160,71 +78,21 @@ def test_hand_built_chains(name, f16, acquire):
 # follows the final conv on the same tile.  shift 0: the pair's chunks 0 and 1 are the final conv's
 # output planes 0 and 1 and are kept in LDS.  shift 16, 32, 48: a valid table as well (the pair's chunk 0
 # still overlaps what the final conv wrote), but its chunks 0 and 1 are other planes: nothing may be kept.
-@functools.lru_cache(maxsize=None)
-def _boundary_case(shift, f16):
-    n, h, w = 2, 36, 52
-    dtype = torch.float16 if f16 else torch.bfloat16
-    g = torch.Generator().manual_seed(17 + shift)
-    A = ops.ActBuffer.alloc(n, h, w, 192, 1, DEV, dtype=dtype)
-    B = ops.ActBuffer.alloc(n, h, w, 192, 1, DEV, dtype=dtype)
-    hold, descs = [], []
-
-    def conv(cin, cout):
-        wt = (torch.randn(cout, cin, 3, 3, generator=g) * (1.5 / (9 * cin) ** 0.5)).to(DEV)
-        b = (torch.randn(cout, generator=g) * 0.1).to(DEV).contiguous()
-        wp = ops.pack_conv3x3(wt, f16=f16)
-        hold.extend([wp, b])
-        return wp, b
-
-    wp, b = conv(192, 64)
-    descs.append(ops.conv3x3_desc(A, 192, wp, b, 64, B, slope=1.0, r1=A, s1=0.2))
-    for cin, slope in ((64, 0.2), (96, 0.35)):
-        wp, b = conv(cin, 32)
-        descs.append(ops.conv3x3_desc(B, cin, wp, b, 32, B, x_coff=shift, y_coff=shift + cin, slope=slope))
-    xs = [(torch.randn(n, 192, h, w, generator=torch.Generator().manual_seed(60 + i)).to(DEV),
-           torch.randn(n, 192, h, w, generator=torch.Generator().manual_seed(80 + i)).to(DEV)) for i in range(3)]
-    refs = []
-    for xa, xb in xs:
-        _fill_ab(A, B, xa, xb)
-        for d in descs:
-            ops.launch_conv3x3(d)
-        torch.cuda.synchronize()
-        refs.append((A.t.clone(), B.t.clone()))
-    return A, B, descs, xs, refs, hold
+# Both buffers start full of data: B's channels the final conv does not write are inputs of the shifted pair.
+SHIFTS = (0, 16, 32, 48)
 
 
-def _fill_ab(A, B, xa, xb):
-    """Both buffers start full of data: B's channels the final conv does not write are inputs of the
-    shifted pair."""
-    for buf, x in ((A, xa), (B, xb)):
-        buf.t.zero_()
-        buf.set_nchw(x, 0)
+def boundary_case(shift):
+    layers = ((192, 64, 0, 0, 1, 0, 1.0, True),
+              H.growth(64, shift + 64, 0.2, 1, shift), H.growth(96, shift + 96, 0.35, 1, shift))
+    return H.ChainCase(layers, in_ch=(192, 192), wseed=17 + shift, xseeds=((60, 80), (61, 81), (62, 82)))
 
 
 @pytest.mark.parametrize("f16", [True, False], ids=["fp16", "bf16"])
-@pytest.mark.parametrize("shift", [0, 16, 32, 48])
+@pytest.mark.parametrize("shift", SHIFTS)
 def test_final_conv_then_pair_on_the_same_tile(shift, f16):
-    A, B, descs, xs, refs, _ = _boundary_case(shift, f16)
-    chain = engine.ConvChain(descs, A, DEV, acquire=False, variant=0)
-    stream = ops._stream()
-    for (xa, xb), (ra, rb) in zip(xs, refs):
-        _fill_ab(A, B, xa, xb)
-        ops.check(chain.fn(ctypes.byref(chain.desc), stream), "isr_conv_chain")
-        torch.cuda.synchronize()
-        assert not chain.failed(), "a chain dependency wait gave up"
-        assert torch.equal(A.t, ra), "the chain changed its input buffer"
-        assert torch.equal(B.t, rb), \
-            f"chain differs from the per-conv launches: max {(B.t.float() - rb.float()).abs().max().item()}"
-    assert paired_layers(chain) == 2, "the two growth convs behind the final conv pair"
-
-
-def _child(mode):
-    """One value of the switch in a fresh process (the library reads it once)."""
-    env = dict(os.environ, ISR_TRUNK_KEEP=str(mode))
-    r = subprocess.run([sys.executable, str(Path(__file__).resolve())], env=env, cwd=ROOT, capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    r0 = H.check_chain(H.chain_case(boundary_case(shift), 2, 36, 52, f16), 0, acquire=False)
+    assert r0 == 2, "the two growth convs behind the final conv pair"
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2], ids=["off", "on", "handoff_only"])
@@ -233,7 +101,8 @@ def test_switch_values(mode):
     phase-2 hand-off only, not across a final conv): all equal the per-conv launches, on a growth-only
     chain with both pairs in place and on a one-block generator of 3 x 3 tiles (two final convs, each
     followed by a pair on the same tile)."""
-    assert _child(mode) == {"keep": mode, "fp16": 4, "bf16": 4, "generator": 12}
+    want = {"keep": mode, "fp16": 4, "bf16": 4, "generator": 12}
+    assert H.switch_child(__file__, {"ISR_TRUNK_KEEP": str(mode)}) == want
 
 
 if __name__ == "__main__":
@@ -243,7 +112,7 @@ if __name__ == "__main__":
     res = {"keep": int(os.environ["ISR_TRUNK_KEEP"])}
     for f16 in (True, False):
         res["fp16" if f16 else "bf16"] = _check_chain("rdb4_slopes", 2, 36, 52, f16, False)
-    gw, xs, refs = _model_case(1, 48, 96, 1, True)
-    outs, res["generator"] = _run(gw, xs, chain=True)
+    gw, xs, refs = H.model_case(1, 48, 96, 1, True, 11)
+    outs, res["generator"] = H.run_plan(gw, xs, chain=True)
     assert all(torch.equal(o, r) for o, r in zip(outs, refs)), "chain differs from the per-conv launches"
     print(json.dumps(res))
