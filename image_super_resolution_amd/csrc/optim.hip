@@ -101,7 +101,8 @@ __global__ __launch_bounds__(MT_THREADS) void mt_sumsq_kernel(const isr_mt_tenso
     }
 }
 
-// total_norm = sqrt(sum partial) (double accumulation); coef = min(1, max_norm / (total_norm + 1e-6))
+// total_norm = sqrt(sum partial) (double accumulation); coef = clamp(max_norm / (total_norm + 1e-6), max=1),
+// NaN kept as torch.clamp keeps it
 __global__ __launch_bounds__(MT_THREADS) void clip_coef_kernel(const float* __restrict__ partial, int n,
                                                                float max_norm, float* __restrict__ out) {
     double acc = 0.0;
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(MT_THREADS) void clip_coef_kernel(const float* __re
         const float norm = (float)sqrt(s);
         const float coef = max_norm / (norm + 1e-6f);
         out[0] = norm;
-        out[1] = coef < 1.f ? coef : 1.f;
+        out[1] = coef > 1.f ? 1.f : coef;  // torch.clamp(coef, max=1): a NaN coefficient stays NaN
     }
 }
 

@@ -9,6 +9,8 @@ utils/models.py:31-40 ModelEMA.update).
 * `clip_grad_norm_(params, max_norm)` — torch.nn.utils.clip_grad_norm_ (L2):
   per-chunk sums of squares → total norm and clip coefficient on the device →
   in-place scale; no host sync; returns the total norm as a 0-d device tensor.
+  A NaN gradient entry makes the norm, the coefficient and so every gradient NaN,
+  an inf entry gives coefficient 0, as torch's clamp(max=1.0) does.
 * `ema_update_(ema_tensors, model_tensors, d)` — v = v*d + (1-d)*m.
 
 Tensors must be dense (contiguous or channels_last) and share strides with
@@ -198,6 +200,8 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_i
     dev = grads[0].device
     rows = [(0, g.data_ptr(), 0, 0, g.numel()) for g in grads]
     pt, ch, n = _CLIP_CACHE.get(rows, dev)
+    if n == 0:  # zero-element gradients only: norm 0, nothing to scale
+        return torch.zeros((), dtype=torch.float32, device=dev)
     partial = torch.empty(n, dtype=torch.float32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
     s = ops._stream()
@@ -226,6 +230,8 @@ def ema_update_(ema: list[torch.Tensor], model: list[torch.Tensor], d: float) ->
             keep.append(m)  # alive until the launch is enqueued (stream-ordered reuse after that)
         rows.append((v.data_ptr(), m.data_ptr(), 0, 0, v.numel()))
     pt, ch, n = _EMA_CACHE.get(rows, ema[0].device)
+    if n == 0:  # zero-element tensors only
+        return
     _lib.check(_lib.load().isr_mt_lerp_guarded(pt.data_ptr(), ch.data_ptr(), n, float(d), _GUARD[0],
                                                 ops._stream()), "isr_mt_lerp")
     ops.bump_param_epoch()

@@ -500,7 +500,8 @@ int isr_mt_adam(const isr_mt_tensor* tensors, const isr_mt_chunk* chunks, int32_
 /* partial[k] = sum of g^2 over chunk k. */
 int isr_mt_sumsq(const isr_mt_tensor* tensors, const isr_mt_chunk* chunks, int32_t nchunks, float* partial,
                  isr_stream_t s);
-/* out[0] = sqrt(sum partial), out[1] = min(1, max_norm / (out[0] + 1e-6)) — clip_grad_norm_'s coefficient. */
+/* out[0] = sqrt(sum partial), out[1] = max_norm / (out[0] + 1e-6) clamped to at most 1 — clip_grad_norm_'s
+ * coefficient.  A NaN norm gives a NaN coefficient, as torch.clamp(coef, max=1.0) does. */
 int isr_clip_coef(const float* partial, int32_t n, float max_norm, float* out, isr_stream_t s);
 /* g *= *coef over every chunk (clip_grad_norm_'s in-place scaling). */
 int isr_mt_scale(const isr_mt_tensor* tensors, const isr_mt_chunk* chunks, int32_t nchunks, const float* coef,

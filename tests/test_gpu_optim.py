@@ -1,10 +1,15 @@
 """Multi-tensor optimiser kernels (optim.py / isr_mt_*) vs torch's own
-Adam, clip_grad_norm_ and the EMA lerp on the same tensors."""
+Adam, clip_grad_norm_ and the EMA lerp on the same tensors, and FusedAdam's
+plumbing (per-parameter step counts, parameter groups, the pointer-table upload
+ring, checkpoint resume) bit for bit against tests/optim_ref.py.  The kernels
+themselves are pinned in test_gpu_optim_exact.py."""
 import copy
 
+import numpy as np
 import pytest
 import torch
 
+import optim_ref as R
 from image_super_resolution_amd import models, optim
 
 pytestmark = pytest.mark.gpu
@@ -51,6 +56,130 @@ def test_fused_adam_matches_torch(wd):
     oc = torch.optim.Adam(b, lr=1e-3)
     oc.load_state_dict(st)
     assert float(oc.state_dict()["state"][0]["step"]) == 5.0
+
+
+def _bits(t):
+    """The int32 words of a tensor in its logical order (sign of zero and NaN payloads count)."""
+    return np.ascontiguousarray(t.detach().cpu().numpy()).view(np.int32)
+
+
+def test_fused_adam_exact_over_twenty_steps():
+    """20 steps with freshly allocated gradients (all kept alive, so no pointer recurs): p, exp_avg and
+    exp_avg_sq equal optim_ref.adam_step in every bit after every step.  Two groups with their own lr
+    and weight decay under LinearLR; a parameter without a gradient on every third step, whose step
+    count falls behind and splits its group's launch in two; a channels_last and a zero-element
+    parameter.  Up to four pointer tables a step: the 16-slot upload ring wraps after four steps and the
+    four-entry pointer cache evicts on every one."""
+    gen = torch.Generator().manual_seed(5)
+
+    def new(shape, cl=False):
+        t = torch.randn(shape, generator=gen).to(DEV)
+        return t.to(memory_format=torch.channels_last) if cl else t
+
+    ga = [new((64, 3, 9, 9)), new((7,)), new((70001,)), new((0,)), new((33,))]
+    gb = [new((32, 64, 3, 3)), new((8, 16, 3, 3), cl=True), new((2 * optim.CHUNK + 5,)), new((1028,))]
+    lazy = {4, 8}  # ga[4] and gb[3]
+    ps = [p.requires_grad_() for p in ga + gb]
+    opt = optim.FusedAdam([dict(params=ps[:5], lr=1e-3, weight_decay=0.0),
+                           dict(params=ps[5:], lr=3e-4, weight_decay=1e-2)], betas=(0.9, 0.999))
+    sched = torch.optim.lr_scheduler.LinearLR(opt, 1, 0.01, total_iters=20)
+    ref = [[np.ascontiguousarray(p.detach().cpu().numpy()), np.zeros(p.shape, np.float32),
+            np.zeros(p.shape, np.float32), 0] for p in ps]
+    alive = []
+    for step in range(20):
+        for k, p in enumerate(ps):
+            if k in lazy and step % 3 == 1:
+                p.grad = None
+                continue
+            p.grad = new(p.shape, cl=not p.is_contiguous())
+            alive.append(p.grad)
+            group = opt.param_groups[0 if k < 5 else 1]
+            ref[k][3] += 1
+            args = R.adam_args(group["lr"], 0.9, 0.999, group["eps"], group["weight_decay"], float(ref[k][3]))
+            ref[k][:3] = R.adam_step(ref[k][0], p.grad.cpu().numpy(), ref[k][1], ref[k][2], args)
+        opt.step(), sched.step()
+        for k, p in enumerate(ps):
+            st = opt.state[p]
+            assert float(st["step"]) == ref[k][3], (step, k)
+            for name, got, want in (("p", p, ref[k][0]), ("exp_avg", st["exp_avg"], ref[k][1]),
+                                    ("exp_avg_sq", st["exp_avg_sq"], ref[k][2])):
+                assert np.array_equal(_bits(got), want.view(np.int32)), f"step {step}, parameter {k}: {name} differs"
+    assert ref[4][3] == 13 and ref[0][3] == 20
+    assert opt.state[ps[6]]["exp_avg"].is_contiguous(memory_format=torch.channels_last)
+
+
+def test_zero_element_tensors_are_harmless():
+    """A zero-element parameter has no chunk: alone it makes every launch empty (no launch at all),
+    among others it changes nothing."""
+    z = torch.empty(0, device=DEV).requires_grad_()
+    z.grad = torch.empty(0, device=DEV)
+    opt = optim.FusedAdam([z], lr=1e-3)
+    opt.step()
+    assert float(opt.state[z]["step"]) == 1.0
+    norm = optim.clip_grad_norm_([z], 10)
+    assert norm.item() == 0.0 and norm.is_cuda
+    optim.ema_update_([z.data], [z.detach().clone()], 0.5)
+    optim.ema_update_([], [], 0.5)
+    # among others
+    gen = torch.Generator().manual_seed(6)
+    a = torch.randn(1028, generator=gen).to(DEV).requires_grad_()
+    a.grad = torch.randint(-3, 4, (1028,), generator=gen).float().to(DEV)
+    b = a.detach().clone().requires_grad_()
+    b.grad = a.grad.clone()
+    na, nb = optim.clip_grad_norm_([z, a], 10), optim.clip_grad_norm_([b], 10)
+    assert np.array_equal(_bits(na), _bits(nb)) and np.array_equal(_bits(a.grad), _bits(b.grad))
+    optim.FusedAdam([z, a], lr=1e-3).step(), optim.FusedAdam([b], lr=1e-3).step()
+    assert np.array_equal(_bits(a), _bits(b))
+    ea, eb = torch.ones(1028, device=DEV), torch.ones(1028, device=DEV)
+    optim.ema_update_([z.data, ea], [z.data, a.data], 0.75), optim.ema_update_([eb], [b.data], 0.75)
+    assert np.array_equal(_bits(ea), _bits(eb)) and not bool((ea == 1).all())
+
+
+def test_resume_from_torch_adam_state():
+    """The direction training uses: three steps of torch.optim.Adam, its state_dict() loaded into a
+    FusedAdam over clones of the parameters, three more steps of each on the same gradients."""
+    a = _params(3)
+    oa = torch.optim.Adam(a, lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-2, foreach=False)
+    for step in range(3):
+        _grads(a, 20 + step)
+        oa.step()
+    b = [p.detach().clone().requires_grad_() for p in a]
+    ob = optim.FusedAdam(b, lr=5e-2, betas=(0.5, 0.9))  # every hyper-parameter comes from the state
+    ob.load_state_dict(copy.deepcopy(oa.state_dict()))
+    assert ob.param_groups[0]["lr"] == 1e-3 and tuple(ob.param_groups[0]["betas"]) == (0.9, 0.999)
+    for step in range(3, 6):
+        _grads(a, 20 + step)
+        _grads(b, 20 + step)
+        oa.step(), ob.step()
+    for x, y in zip(a, b):
+        assert float(ob.state[y]["step"]) == 6.0
+        torch.testing.assert_close(y, x, rtol=2e-6, atol=2e-7)
+        torch.testing.assert_close(ob.state[y]["exp_avg"], oa.state[x]["exp_avg"], rtol=2e-6, atol=2e-7)
+
+
+def test_resume_from_fused_adam_state_is_bit_identical():
+    """Three steps, state_dict() into a second FusedAdam over clones, three more: the same bits as six
+    uninterrupted steps."""
+    a, b = _params(4), _params(4)
+    oa = optim.FusedAdam(a, lr=1e-3, weight_decay=1e-2)
+    ob = optim.FusedAdam(b, lr=1e-3, weight_decay=1e-2)
+    for step in range(3):
+        _grads(a, 30 + step)
+        _grads(b, 30 + step)
+        oa.step(), ob.step()
+    c = [p.detach().clone(memory_format=torch.preserve_format).requires_grad_() for p in b]
+    oc = optim.FusedAdam(c, lr=7e-1)
+    oc.load_state_dict(copy.deepcopy(ob.state_dict()))
+    del ob
+    for step in range(3, 6):
+        _grads(a, 30 + step)
+        _grads(c, 30 + step)
+        oa.step(), oc.step()
+    for x, y in zip(a, c):
+        assert float(oc.state[y]["step"]) == 6.0
+        assert np.array_equal(_bits(x), _bits(y))
+        assert np.array_equal(_bits(oa.state[x]["exp_avg"]), _bits(oc.state[y]["exp_avg"]))
+        assert np.array_equal(_bits(oa.state[x]["exp_avg_sq"]), _bits(oc.state[y]["exp_avg_sq"]))
 
 
 def test_clip_grad_norm_matches_torch():
