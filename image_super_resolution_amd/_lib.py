@@ -141,6 +141,13 @@ class IsrYuvDesc(ctypes.Structure):
                 ("dst", c_void_p)]
 
 
+class IsrYuv16Desc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("layout", c_int32), ("siting", c_int32),
+                ("full_range", c_int32), ("depth", c_int32), ("shift", c_int32), ("rgb_kind", c_int32),
+                ("fwd", c_int32 * 9), ("inv", c_int32 * 5), ("mean", c_float * 3), ("inv_std", c_float * 3),
+                ("src", c_void_p), ("dst", c_void_p)]
+
+
 HLS_PARTIAL_BLOCKS = 32  # ISR_HLS_PARTIAL_BLOCKS
 MT_TENSOR_BYTES = 40 # isr_mt_tensor: 4 pointers + int64
 MT_CHUNK_BYTES = 16   # isr_mt_chunk: int32 t, int32 len, int64 start
@@ -224,6 +231,9 @@ SIGNATURES = {
     "isr_yuv_coeffs": (c_int32, [c_int32, c_int32, c_void_p, c_void_p]),
     "isr_yuv420_to_rgb_u8": (c_int32, [POINTER(IsrYuvDesc), c_void_p]),
     "isr_rgb_to_yuv420_u8": (c_int32, [POINTER(IsrYuvDesc), c_void_p]),
+    "isr_yuv_coeffs_depth": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "isr_yuv420_to_rgb_16": (c_int32, [POINTER(IsrYuv16Desc), c_void_p]),
+    "isr_rgb_to_yuv420_16": (c_int32, [POINTER(IsrYuv16Desc), c_void_p]),
     "isr_last_error": (ctypes.c_char_p, []),
     "isr_version": (c_int32, []),
 }

@@ -65,6 +65,7 @@ int iso_noise_dispatch(const isr_iso_noise_desc* d, hipStream_t s);
 int resample_u8_dispatch(const isr_resample_desc* d, hipStream_t s);
 int blur_u8_dispatch(const isr_blur_desc* d, hipStream_t s);
 int yuv_dispatch(const isr_yuv_desc* d, int to_rgb, hipStream_t s);
+int yuv16_dispatch(const isr_yuv16_desc* d, int to_rgb, hipStream_t s);
 }  // namespace isr
 
 static thread_local char g_err[512] = "";
@@ -909,6 +910,58 @@ int isr_yuv420_to_rgb_u8(const isr_yuv_desc* d, isr_stream_t s) {
 int isr_rgb_to_yuv420_u8(const isr_yuv_desc* d, isr_stream_t s) {
     if (int rc = yuv_ok("rgb_to_yuv420_u8", d)) return rc;
     return launched(isr::yuv_dispatch(d, 0, (hipStream_t)s), "rgb_to_yuv420_u8");
+}
+
+int isr_yuv_coeffs_depth(int matrix, int full_range, int depth, int32_t* fwd, int32_t* inv) {
+    if (!fwd || !inv) return fail(ISR_ERR_BAD_DESC, "yuv_coeffs_depth: null fwd / inv");
+    switch (isr::yuv_coeffs_depth(matrix, full_range, depth, fwd, inv)) {
+        case 0: break;
+        case 1: return fail(ISR_ERR_UNSUPPORTED, "yuv_coeffs_depth: unknown matrix %d (ISR_YUV_BT601, BT709 = 0, 1)", matrix);
+        default: return fail(ISR_ERR_UNSUPPORTED, "yuv_coeffs_depth: depth %d (8 or 10)", depth);
+    }
+    g_err[0] = 0;
+    return ISR_OK;
+}
+
+static int yuv16_ok(const char* what, const isr_yuv16_desc* d, int to_rgb) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "%s: null descriptor", what);
+    if (!d->src || !d->dst) return fail(ISR_ERR_BAD_DESC, "%s: null src / dst", what);
+    if (d->dst == d->src) return fail(ISR_ERR_BAD_DESC, "%s: dst must not be src", what);
+    if (int rc = batch_ok(what, d->n, d->h, d->w, false)) return rc;
+    if (d->h < 2 || d->w < 2 || d->h % 2 || d->w % 2)
+        return fail(ISR_ERR_BAD_DESC, "%s: 4:2:0 needs even h and w of at least 2, got %dx%d", what, d->h, d->w);
+    if ((long long)d->h * d->w > (1ll << 28))
+        return fail(ISR_ERR_UNSUPPORTED, "%s: h*w = %lld is more than 2^28", what, (long long)d->h * d->w);
+    if (d->layout != ISR_YUV_I420 && d->layout != ISR_YUV_NV12)
+        return fail(ISR_ERR_UNSUPPORTED, "%s: unknown layout %d (ISR_YUV_I420, NV12 = 0, 1)", what, d->layout);
+    if (d->siting != ISR_YUV_SITING_LEFT && d->siting != ISR_YUV_SITING_CENTER)
+        return fail(ISR_ERR_UNSUPPORTED, "%s: unknown siting %d (ISR_YUV_SITING_LEFT, CENTER = 0, 1)", what, d->siting);
+    if (d->depth != 10) return fail(ISR_ERR_UNSUPPORTED, "%s: depth %d (10 only)", what, d->depth);
+    if (d->shift < 0 || d->shift + d->depth > 16)
+        return fail(ISR_ERR_UNSUPPORTED, "%s: shift %d + depth %d does not fit a 16-bit word", what, d->shift, d->depth);
+    if (d->rgb_kind != ISR_RGB_U16 && d->rgb_kind != ISR_RGB_NORM_F32 && d->rgb_kind != ISR_RGB_TANH_F32)
+        return fail(ISR_ERR_UNSUPPORTED, "%s: unknown rgb_kind %d (ISR_RGB_U16, NORM_F32, TANH_F32 = 0, 1, 2)", what,
+                    d->rgb_kind);
+    if (d->rgb_kind == (to_rgb ? ISR_RGB_TANH_F32 : ISR_RGB_NORM_F32))
+        return fail(ISR_ERR_UNSUPPORTED, "%s: rgb_kind %d belongs to the other direction (%s)", what, d->rgb_kind,
+                    to_rgb ? "ISR_RGB_TANH_F32 is an input of rgb_to_yuv420_16" : "ISR_RGB_NORM_F32 is an output of yuv420_to_rgb_16");
+    const void* frames = to_rgb ? d->src : (const void*)d->dst;
+    const void* rgb = to_rgb ? (const void*)d->dst : d->src;
+    if (!aligned(2, {frames})) return fail(ISR_ERR_BAD_DESC, "%s: frames of 16-bit words must be 2-byte aligned", what);
+    if (!aligned(d->rgb_kind == ISR_RGB_U16 ? 2 : 4, {rgb}))
+        return fail(ISR_ERR_BAD_DESC, "%s: the RGB side must be %s", what,
+                    d->rgb_kind == ISR_RGB_U16 ? "2-byte aligned (uint16)" : "4-byte aligned (fp32)");
+    return ISR_OK;
+}
+
+int isr_yuv420_to_rgb_16(const isr_yuv16_desc* d, isr_stream_t s) {
+    if (int rc = yuv16_ok("yuv420_to_rgb_16", d, 1)) return rc;
+    return launched(isr::yuv16_dispatch(d, 1, (hipStream_t)s), "yuv420_to_rgb_16");
+}
+
+int isr_rgb_to_yuv420_16(const isr_yuv16_desc* d, isr_stream_t s) {
+    if (int rc = yuv16_ok("rgb_to_yuv420_16", d, 0)) return rc;
+    return launched(isr::yuv16_dispatch(d, 0, (hipStream_t)s), "rgb_to_yuv420_16");
 }
 
 }  // extern "C"

@@ -22,7 +22,10 @@ encoder, bitrate ∝ output megapixels) — rebuilt around the MI355X path:
   yuv420p or nv12: half the bytes of rgb24 / bgr24, what decoders produce and encoders take) and the
   colour conversion runs in the captured graph (yuv.py, csrc/yuv.hip) in place of the layout copies;
   `Y4MReader` / `Y4MRecorder` read and write YUV4MPEG2 (.y4m) files, `RawYUVReader` headerless
-  I420 / NV12, again without ffmpeg.
+  I420 / NV12, again without ffmpeg;
+* a side whose pix_fmt is yuv420p10le or p010le carries 10-bit samples in 16-bit words (what HEVC Main10
+  and AV1 decoders hand over): its frames convert straight to the head's normalised fp32 input and
+  straight from the tail's fp32 tanh (csrc/yuv16.hip), in the same graph, with no 8-bit step between.
 
 Reference bugs deliberately not reproduced: the frame is
 normalised once (rs.py:63 normalises before a TorchScript Model that normalises
@@ -60,7 +63,8 @@ def have_ffmpeg() -> bool:
 
 # ----------------------------------------------------------------------------- sources
 def ffmpeg_reader_cmd(src: str | Path, pix_fmt: str = "rgb24") -> list[str]:
-    """FFmpegVideoReader's decoder argv: raw frames of `pix_fmt` (rgb24, yuv420p or nv12) to a pipe."""
+    """FFmpegVideoReader's decoder argv: raw frames of `pix_fmt` (rgb24, yuv420p, nv12, yuv420p10le or
+    p010le) to a pipe."""
     if pix_fmt != "rgb24" and pix_fmt not in yuvmod.PIX_FMTS:
         raise ValueError(f"unknown pix_fmt {pix_fmt!r}; rgb24, {', '.join(yuvmod.PIX_FMTS)}")
     return ["ffmpeg", "-v", "quiet", "-i", Path(src).as_posix(), "-f", "rawvideo", "-pix_fmt", pix_fmt, "pipe:"]
@@ -86,8 +90,7 @@ class FFmpegVideoReader:
         self.frame_shape = (self.height, self.width, 3)
         if pix_fmt != "rgb24":  # frames as [3h/2, w] bytes; the stream's own tags are not read: YUVFormat's defaults
             self.yuv = YUVFormat.of_pix_fmt(pix_fmt)
-            yuvmod.check_size(self.height, self.width)
-            self.frame_shape = (3 * self.height // 2, self.width)
+            self.frame_shape = yuvmod.frame_shape(self.height, self.width, self.yuv.depth)  # 10 bits: [3h/2, 2w]
 
     def _probe(self, src: Path) -> None:
         if not have_ffmpeg():
@@ -147,24 +150,33 @@ Y4M_TAG = {"center": "420jpeg", "left": "420mpeg2"}
 
 
 def y4m_header(width: int, height: int, fps, yuv: YUVFormat) -> bytes:
-    """The YUV4MPEG2 stream header of progressive 8-bit 4:2:0 frames in `yuv`'s siting and range."""
+    """The YUV4MPEG2 stream header of progressive 4:2:0 frames in `yuv`'s siting and range.  10-bit frames
+    are tagged C420p10 (with ffmpeg's XYSCSS=420P10), which names no siting and is read as left: a
+    center-sited 10-bit format is refused."""
     yuvmod.check_size(height, width)
     if yuv.layout != "i420":
         raise ValueError("a .y4m file holds planar I420 frames, not NV12")
     rate = Fraction(fps).limit_denominator(1001)
     rng = "FULL" if yuv.full_range else "LIMITED"
-    return (f"YUV4MPEG2 W{width} H{height} F{rate.numerator}:{rate.denominator} Ip A1:1 C{Y4M_TAG[yuv.siting]} "
+    if yuv.depth == 10:
+        if yuv.siting != "left":
+            raise ValueError("a 10-bit .y4m file (C420p10) has no tag for center chroma siting: use siting 'left'")
+        tag = "420p10 XYSCSS=420P10"
+    else:
+        tag = Y4M_TAG[yuv.siting]
+    return (f"YUV4MPEG2 W{width} H{height} F{rate.numerator}:{rate.denominator} Ip A1:1 C{tag} "
             f"XCOLORRANGE={rng}\n").encode("ascii")
 
 
-def parse_y4m_header(line: bytes) -> dict:
+def parse_y4m_header(line: bytes, depths=(8,)) -> dict:
     """width, height, fps and yuv (a YUVFormat, matrix "auto") of a YUV4MPEG2 header line.  8-bit
-    progressive 4:2:0 only: any other C or I tag raises a ValueError naming it."""
+    progressive 4:2:0 only: any other C or I tag raises a ValueError naming it.  With 10 among `depths`,
+    C420p10 is taken too: depth 10, siting left."""
     tags = line.decode("ascii", "replace").split()
     if not tags or tags[0] != Y4M_MAGIC.decode():
         raise ValueError("not a YUV4MPEG2 stream (no YUV4MPEG2 magic)")
     w = h = None
-    fps, siting, full = 30.0, "center", False
+    fps, siting, full, depth = 30.0, "center", False, 8
     for t in tags[1:]:
         k, v = t[0], t[1:]
         if k == "W":
@@ -178,21 +190,25 @@ def parse_y4m_header(line: bytes) -> dict:
             if v not in ("p", "?"):
                 raise ValueError(f"y4m: interlacing tag {t!r} is not supported (progressive Ip / I? only)")
         elif k == "C":
-            if v not in Y4M_SITING:
+            if v == "420p10" and 10 in depths:
+                siting, depth = "left", 10
+            elif v not in Y4M_SITING or 8 not in depths:
                 raise ValueError(f"y4m: chroma tag {t!r} is not supported (8-bit C420jpeg, C420, C420mpeg2 only)")
-            siting = Y4M_SITING[v]
+            else:
+                siting, depth = Y4M_SITING[v], 8
         elif t.startswith("XCOLORRANGE="):
             full = t.split("=", 1)[1].upper() == "FULL"
     if w is None or h is None:
         raise ValueError("y4m: the header has no W / H tag")
     yuvmod.check_size(h, w)
-    return {"width": w, "height": h, "fps": fps, "yuv": YUVFormat("i420", "auto", full, siting)}
+    return {"width": w, "height": h, "fps": fps, "yuv": YUVFormat("i420", "auto", full, siting, depth)}
 
 
 class Y4MReader:
     """The frames of a YUV4MPEG2 (.y4m) file as uint8 [3h/2, w] arrays (a frame's bytes in order: the Y
     plane's rows, then U, then V).  `yuv` holds the header's siting and range; a truncated last frame
-    ends the stream."""
+    ends the stream.  A C420p10 file: frames of [3h/2, 2w] bytes, little-endian 16-bit words, `yuv.depth`
+    10 and `pix_fmt` yuv420p10le."""
     pix_fmt = "yuv420p"
 
     def __init__(self, src: str | Path):
@@ -200,9 +216,10 @@ class Y4MReader:
         with open(self.src, "rb") as f:
             line = f.readline(4096)
             self._data0 = f.tell()
-        meta = parse_y4m_header(line)
+        meta = parse_y4m_header(line, depths=(8, 10))
         self.width, self.height, self.fps, self.yuv = meta["width"], meta["height"], meta["fps"], meta["yuv"]
-        self.frame_shape = (3 * self.height // 2, self.width)
+        self.pix_fmt = self.yuv.pix_fmt
+        self.frame_shape = yuvmod.frame_shape(self.height, self.width, self.yuv.depth)
         # "FRAME\n" carries no parameters in the files encoders write: the count is exact for those
         self.total_frame = (self.src.stat().st_size - self._data0) // (math.prod(self.frame_shape) + 6)
 
@@ -225,18 +242,20 @@ class Y4MReader:
 
 class RawYUVReader:
     """Headerless 4:2:0 frames (I420 or NV12, 3 h w / 2 bytes each, back to back) from a file, as uint8
-    [3h/2, w] arrays."""
+    [3h/2, w] arrays; with depth 10 (yuv420p10le / p010le words) 3 h w bytes each, as [3h/2, 2w]."""
 
-    def __init__(self, src: str | Path, width: int, height: int, fps: float = 30.0, layout: str = "i420"):
+    def __init__(self, src: str | Path, width: int, height: int, fps: float = 30.0, layout: str = "i420",
+                 depth: int = 8):
         self.src, self.width, self.height, self.fps = Path(src), width, height, fps
-        self.yuv = YUVFormat(layout)
+        self.yuv = YUVFormat(layout, depth=depth)
         self.pix_fmt = self.yuv.pix_fmt
-        fb = yuvmod.frame_bytes(height, width)
+        fb = yuvmod.frame_bytes(height, width, depth)
         size = self.src.stat().st_size
         if size % fb:
-            raise ValueError(f"{src}: {size} bytes is not a whole number of {width}x{height} 4:2:0 frames")
+            raise ValueError(f"{src}: {size} bytes is not a whole number of {width}x{height} 4:2:0 frames"
+                             + (f" of {depth} bits" if depth != 8 else ""))
         self.total_frame = size // fb
-        self.frame_shape = (3 * height // 2, width)
+        self.frame_shape = yuvmod.frame_shape(height, width, depth)
 
     def __len__(self):
         return self.total_frame
@@ -270,7 +289,8 @@ class SyntheticVideo:
 def open_video(src: str | Path, width: int | None = None, height: int | None = None, fps: float = 30.0,
                pix_fmt: str = "rgb24"):
     """`dataset_for_inference` equivalent: ffmpeg for container formats (decoding to `pix_fmt`), raw for
-    .rgb/.raw, YUV4MPEG2 for .y4m, headerless I420 for .yuv/.i420 and NV12 for .nv12."""
+    .rgb/.raw, YUV4MPEG2 for .y4m, headerless I420 for .yuv/.i420 and NV12 for .nv12 (of 10-bit words when
+    `pix_fmt` is yuv420p10le or p010le)."""
     src = Path(src)
     suffix = src.suffix.lower()
     if suffix in RGB_FORMATS:
@@ -282,7 +302,8 @@ def open_video(src: str | Path, width: int | None = None, height: int | None = N
     if suffix in YUV_FORMATS:
         if not (width and height):
             raise ValueError("raw 4:2:0 input needs --video_size WxH")
-        return RawYUVReader(src, width, height, fps, "nv12" if suffix == ".nv12" else "i420")
+        return RawYUVReader(src, width, height, fps, "nv12" if suffix == ".nv12" else "i420",
+                            yuvmod.PIX_FMT_DEPTH.get(pix_fmt, 8))
     return FFmpegVideoReader(src, pix_fmt)
 
 
@@ -338,13 +359,15 @@ class FFMPEG_recorder:  # noqa: N801  (reference class name, utils/ffmpeg.py:28)
         if pix_fmt != "bgr24":  # 4:2:0 frames through the pipe: ffmpeg converts nothing, so tell it what they are
             self.yuv = (yuv or YUVFormat.of_pix_fmt(pix_fmt)).resolved(height)
             if self.yuv.pix_fmt != pix_fmt:
-                raise ValueError(f"FFMPEG_recorder: pix_fmt {pix_fmt!r} with a {self.yuv.layout} YUVFormat")
+                raise ValueError(f"FFMPEG_recorder: pix_fmt {pix_fmt!r} with a {self.yuv.pix_fmt} YUVFormat")
             tags = ['-colorspace', 'bt709' if self.yuv.matrix == 'bt709' else 'smpte170m',
                     '-color_range', 'pc' if self.yuv.full_range else 'tv',
                     '-chroma_sample_location', self.yuv.siting]
         source = ['-s', f'{width}x{height}', '-pixel_format', pix_fmt, *tags, '-f', 'rawvideo', '-r', f'{self.fps}',
                   '-i', 'pipe:']
-        sink = ['-vcodec', f'{self.codec}', '-pix_fmt', 'yuv420p', *tags, '-b:v', f'{self.bitRate}M', f'{out_path}']
+        # a 10-bit pipe is encoded at 10 bits: the samples the network made are not rounded to 8 again
+        sink_fmt = 'yuv420p10le' if self.yuv is not None and self.yuv.depth == 10 else 'yuv420p'
+        sink = ['-vcodec', f'{self.codec}', '-pix_fmt', sink_fmt, *tags, '-b:v', f'{self.bitRate}M', f'{out_path}']
         self.cmd = ['ffmpeg', '-v', 'quiet', '-y', *source, *sink]
         self.process = None
         if dry_run:
@@ -443,7 +466,7 @@ class Y4MRecorder:
         self.yuv = yuv or YUVFormat()
         width, height = videoDimensions
         header = y4m_header(width, height, fps, self.yuv)
-        self._bytes = yuvmod.frame_bytes(height, width)
+        self._bytes = yuvmod.frame_bytes(height, width, self.yuv.depth)
         self._f = open(self.save_path, "wb")
         self._f.write(header)
         self.frames = 0
@@ -485,7 +508,10 @@ class FrameUpscaler:
     HIP generator, one captured HIP graph per batch geometry.  `pix_fmt_in` / `pix_fmt_out` of yuv420p
     or nv12 (independently) make that side 8-bit 4:2:0 frames of `yuv_in` / `yuv_out` (a YUVFormat; by
     default limited range, left siting, the matrix by the frame's height), converted by libisr's colour
-    kernels inside the same graph.
+    kernels inside the same graph.  yuv420p10le / p010le make that side 10-bit frames in 16-bit words
+    ([3h/2, 2w] bytes): a 10-bit input converts straight to the head's normalised fp32 input (the plan is
+    built with x_u8=False), a 10-bit output straight from the tail's fp32 tanh (out_u8=False), so no
+    8-bit value stands between the frame and the network on such a side.
 
     `gw` is an engine.GeneratorWeights (tiler.runner_for(model).gw); `mean` /
     `std` the Normalize constants fused into the head kernel."""
@@ -509,21 +535,30 @@ class FrameUpscaler:
             self.yuv_in = self._format(yuv_in, pix_fmt_in, height, width)
         if pix_fmt_out != "bgr24":
             self.yuv_out = self._format(yuv_out, pix_fmt_out, H, W)
-        self.plan = engine.make_plan(gw, batch, height, width, self.device, True, True, mean, std)
-        self.in_frame_shape = (height, width, 3) if self.yuv_in is None else (3 * height // 2, width)
-        self.out_frame_shape = (H, W, 3) if self.yuv_out is None else (3 * H // 2, W)
+        in10 = self.yuv_in is not None and self.yuv_in.depth == 10
+        out10 = self.yuv_out is not None and self.yuv_out.depth == 10
+        self.plan = engine.make_plan(gw, batch, height, width, self.device, not in10, not out10, mean, std)
+        self.in_frame_shape = ((height, width, 3) if self.yuv_in is None
+                               else yuvmod.frame_shape(height, width, self.yuv_in.depth))
+        self.out_frame_shape = (H, W, 3) if self.yuv_out is None else yuvmod.frame_shape(H, W, self.yuv_out.depth)
         self.x_in = torch.zeros((batch, *self.in_frame_shape), dtype=torch.uint8, device=self.device)
-        self.x = torch.empty((batch, 3, height, width), dtype=torch.uint8, device=self.device)
-        self.y = torch.empty(self.plan.out_shape, dtype=torch.uint8, device=self.device)
+        self.x = torch.empty((batch, 3, height, width), dtype=torch.float32 if in10 else torch.uint8, device=self.device)
+        self.y = torch.empty(self.plan.out_shape, dtype=self.plan.out_dtype, device=self.device)
         self.y_out = torch.empty((batch, *self.out_frame_shape), dtype=torch.uint8, device=self.device)
         self.x_hwc = self.x_in if self.yuv_in is None else None  # the rgb-mode names of the staging tensors
         self.bgr = self.y_out if self.yuv_out is None else None
         self._lib = _lib.load()
         self._desc_in = self._desc_out = None
         with torch.cuda.device(self.device):
-            if self.yuv_in is not None:
+            if in10:  # 10-bit words -> the head's normalised fp32 input
+                self._desc_in = yuvmod._desc16(batch, height, width, self.yuv_in, "norm_f32", self.x_in.data_ptr(),
+                                               self.x.data_ptr(), mean, std)
+            elif self.yuv_in is not None:
                 self._desc_in = yuvmod._desc(batch, height, width, self.yuv_in, self.x_in.data_ptr(), self.x.data_ptr())
-            if self.yuv_out is not None:
+            if out10:  # the tail's fp32 tanh -> 10-bit words
+                self._desc_out = yuvmod._desc16(batch, H, W, self.yuv_out, "tanh_f32", self.y.data_ptr(),
+                                                self.y_out.data_ptr())
+            elif self.yuv_out is not None:
                 self._desc_out = yuvmod._desc(batch, H, W, self.yuv_out, self.y.data_ptr(), self.y_out.data_ptr())
         self.stream = torch.cuda.Stream(self.device)
         self.graph = None
@@ -541,19 +576,25 @@ class FrameUpscaler:
     def _format(fmt: YUVFormat | None, pix_fmt: str, height: int, width: int) -> YUVFormat:
         fmt = fmt or YUVFormat.of_pix_fmt(pix_fmt)
         if fmt.pix_fmt != pix_fmt:
-            raise ValueError(f"pix_fmt {pix_fmt!r} with a {fmt.layout} YUVFormat")
+            raise ValueError(f"pix_fmt {pix_fmt!r} with a {fmt.pix_fmt} YUVFormat")
         yuvmod.check_size(height, width)
         return fmt.resolved(height)
 
     def _body(self):
         if self._desc_in is None:
             self.x.copy_(self.x_in.permute(0, 3, 1, 2))
+        elif isinstance(self._desc_in, _lib.IsrYuv16Desc):
+            _lib.check(self._lib.isr_yuv420_to_rgb_16(ctypes.byref(self._desc_in), yuvmod._stream()),
+                       "isr_yuv420_to_rgb_16")
         else:  # 4:2:0 frames -> planar RGB, one kernel in place of the HWC→CHW copy
             _lib.check(self._lib.isr_yuv420_to_rgb_u8(ctypes.byref(self._desc_in), yuvmod._stream()),
                        "isr_yuv420_to_rgb_u8")
         self.plan.run(self.x, self.y)
         if self._desc_out is None:
             self.y_out.copy_(self.y.flip(1).permute(0, 2, 3, 1))  # RGB2BGR + CHW→HWC (utils/datasets.py RGB2BGR)
+        elif isinstance(self._desc_out, _lib.IsrYuv16Desc):
+            _lib.check(self._lib.isr_rgb_to_yuv420_16(ctypes.byref(self._desc_out), yuvmod._stream()),
+                       "isr_rgb_to_yuv420_16")
         else:  # planar RGB -> 4:2:0 frames, in place of the flip / permute copy
             _lib.check(self._lib.isr_rgb_to_yuv420_u8(ctypes.byref(self._desc_out), yuvmod._stream()),
                        "isr_rgb_to_yuv420_u8")

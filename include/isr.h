@@ -822,6 +822,88 @@ typedef struct isr_yuv_desc {
 int isr_yuv420_to_rgb_u8(const isr_yuv_desc* d, isr_stream_t s);
 int isr_rgb_to_yuv420_u8(const isr_yuv_desc* d, isr_stream_t s);
 
+/* ---- YUV 4:2:0 video frames of more than 8 bits ---------------------------------
+ * 10-bit 4:2:0 frames (ffmpeg's yuv420p10le and p010le: what HEVC Main10 and AV1 decoders hand over)
+ * <-> RGB at the same depth, or straight to the head's normalised fp32 input and from the tail's fp32
+ * tanh, so that a 10-bit side of the video path has no 8-bit step.  d = depth = 10 below.
+ *
+ * A sample is a 16-bit little-endian word; a frame is 3 h w bytes, in the layout of the 8-bit section
+ * with words for bytes (ISR_YUV_I420: three planes of words; ISR_YUV_NV12: a Y plane, then rows of w
+ * words U0 V0 U1 V1 ...).  `shift` is the sample's position in its word: 0 for yuv420p10le, 6 for p010le.
+ *   read    sample = (word >> shift) & (2^d - 1): bits outside the field are ignored
+ *   write   word = sample << shift: every other bit is 0
+ *
+ * isr_yuv_coeffs_depth (host, plain C++, no GPU) makes the coefficients as isr_yuv_coeffs does, same
+ * fix(), same ISR_YUV_BITS, same closing of the rows (Y sums to fix(sy), chroma to 0: a grey pixel gives
+ * Cb = Cr = 2^(d-1) exactly), with
+ *   limited  sy = 219 2^(d-8) / (2^d - 1), sc = 224 2^(d-8) / (2^d - 1), oy = 16 2^(d-8)
+ *   full     sy = sc = 1, oy = 0
+ * depth 8 gives isr_yuv_coeffs' integers exactly.  Refused: an unknown matrix and a depth other than 8 or
+ * 10 ISR_ERR_UNSUPPORTED; a null pointer ISR_ERR_BAD_DESC.
+ *
+ * The RGB side, `rgb_kind`:
+ *   ISR_RGB_U16       both directions: planar uint16 [n][3][h][w] of 0 .. 2^d - 1 (on input the low d bits
+ *                     of each word are read)
+ *   ISR_RGB_NORM_F32  yuv -> rgb only: fp32 [n][3][h][w], the head's input
+ *                       x = ((float)v / (float)(2^d - 1) - mean[c]) * inv_std[c]
+ *                     one IEEE division, one subtraction, one multiplication, each rounded once
+ *   ISR_RGB_TANH_F32  rgb -> yuv only: fp32 [n][3][h][w] t, the tail's output, quantised as the tail does
+ *                     for uint8:
+ *                       v = 0 unless t > -1 (NaN, -inf: 0); v = 2^d - 1 if t >= 1; otherwise
+ *                       v = clamp(rint((t + 1.0f) * 0.5f * (float)(2^d - 1))), round-half-even, each
+ *                     operation rounded once in fp32
+ *
+ * The arithmetic is the 8-bit section's with oy as above, 128 -> 2^(d-1), 255 -> 2^d - 1 (clampd clips to
+ * [0, 2^d - 1]), the same sitings, edge replication and D, every stored integer rounded once:
+ *   Y[y][x] = clampd((fwdY . (R, G, B) + oy 65536 + 32768) >> 16)
+ *   C[i][j] = clampd((fwdC . S + 2^(d-1) 65536 D + 32768 D) >> (16 + log2 D))
+ *   R = clampd((cy D (Y - oy) + crv (V* - 2^(d-1) D) + 32768 D) >> (16 + log2 D))
+ *   G = clampd((cy D (Y - oy) + cgu (U* - 2^(d-1) D) + cgv (V* - 2^(d-1) D) + 32768 D) >> (16 + log2 D))
+ *   B = clampd((cy D (Y - oy) + cbu (U* - 2^(d-1) D) + 32768 D) >> (16 + log2 D))
+ * Bounds at d = 10 over isr_yuv_coeffs_depth's four tables (the kernels mask every sample to d bits, so
+ * these hold for any frame):
+ *   rgb -> yuv  the Y sum is at most 65536 1023 + 64 65536 + 32768 < 7.2e7; a chroma sum is at most
+ *               0.5 65536 (8 1023) + 512 65536 8 + 32768 8 < 5.4e8 (left, D = 8): int32 holds both.
+ *   yuv -> rgb  center siting, D = 16.  The luma term cy D (Y - oy) + 32768 D lies in [-7.9e7, 1.175e9]
+ *               (limited: cy = 76533, Y - oy in [-64, 959]) and each chroma product within +-1.138e9
+ *               (cbu <= 138846, bt709 limited, |U* - 512 D| <= 8192): each fits int32 on its own.
+ *               Their sums do not all fit: the blue sum reaches 1.175e9 + 1.135e9 = 2.31e9 (bt709
+ *               limited; bt601 limited 2.26e9) and the red sum 2.138e9, 0.4 % under 2^31 - 1.  So the red
+ *               and the blue sum are formed in 64 bits.  The green sum has two negative coefficients and
+ *               is at most 1.175e9 + 8192 (25750 + 53435) = 1.824e9 (bt601 limited) and at least
+ *               -7.8e7 - 8176 (25750 + 53435) = -7.3e8: int32.  Left siting (D = 8) halves every term.
+ * Other coefficients wrap in the 32-bit terms; they cannot move an access.
+ *
+ * isr_yuv420_to_rgb_16: src frames -> dst RGB (ISR_RGB_U16 or ISR_RGB_NORM_F32).
+ * isr_rgb_to_yuv420_16: src RGB (ISR_RGB_U16 or ISR_RGB_TANH_F32) -> dst frames.
+ * Both are one launch on `s`, stateless: no device table, no workspace, no allocation, no
+ * synchronisation.  n in [1, 65535]; h, w even, >= 2, h w <= 2^28; dst must not be src.  Frames and
+ * uint16 RGB must be 2-byte aligned and fp32 RGB 4-byte aligned (else ISR_ERR_BAD_DESC); 16-byte accesses
+ * are used per plane where w % 16 == 0 and that plane's address allows, element accesses otherwise and
+ * at a ragged right edge.  Refused before any launch: null pointers, odd or too small h, w
+ * (ISR_ERR_BAD_DESC); an unknown layout, siting or rgb_kind, a kind of the other direction, a depth other
+ * than 10, shift < 0 or shift + depth > 16 (ISR_ERR_UNSUPPORTED). */
+#define ISR_RGB_U16 0
+#define ISR_RGB_NORM_F32 1
+#define ISR_RGB_TANH_F32 2
+int isr_yuv_coeffs_depth(int matrix, int full_range, int depth, int32_t* fwd /* [9] */, int32_t* inv /* [5] */);
+
+typedef struct isr_yuv16_desc {
+    int32_t n, h, w;        /* of the RGB image = of the luma plane */
+    int32_t layout;         /* ISR_YUV_I420 / ISR_YUV_NV12 */
+    int32_t siting;         /* ISR_YUV_SITING_LEFT / ISR_YUV_SITING_CENTER */
+    int32_t full_range;     /* 0: oy = 16 2^(depth-8); non-zero: oy = 0 */
+    int32_t depth;          /* 10 */
+    int32_t shift;          /* the sample's position in its word: 0 (yuv420p10le) .. 16 - depth (p010le) */
+    int32_t rgb_kind;       /* ISR_RGB_U16 / ISR_RGB_NORM_F32 / ISR_RGB_TANH_F32 */
+    int32_t fwd[9], inv[5]; /* isr_yuv_coeffs_depth's (each entry point reads its own) */
+    float mean[3], inv_std[3]; /* ISR_RGB_NORM_F32 */
+    const void* src;
+    void* dst;
+} isr_yuv16_desc;
+int isr_yuv420_to_rgb_16(const isr_yuv16_desc* d, isr_stream_t s);
+int isr_rgb_to_yuv420_16(const isr_yuv16_desc* d, isr_stream_t s);
+
 const char* isr_last_error(void);
 int isr_version(void);
 

@@ -32,6 +32,15 @@ what a .y4m header says (default: limited range, left siting, BT.709 at a height
 and BT.601 below, for the input and the output frame each).
 
     python rs.py --model ck.pt --src clip.y4m --save_dir out.y4m
+
+10-bit 4:2:0 (what HEVC Main10 and AV1 decoders hand over): a C420p10 .y4m is read as such; `--pix_fmt
+yuv420p10le|p010le` pipes 10-bit frames from and to ffmpeg and says that a raw .yuv / .i420 / .nv12
+source holds 16-bit words.  The output has the input's depth unless `--out_depth 8|10` says otherwise
+(an 8-bit source written at 10 bits keeps what the network computes below the 8-bit step).  A 10-bit
+side is converted straight to the network's fp32 input and straight from its fp32 output.
+
+    python rs.py --model ck.pt --src clip.mkv --save_dir out.mp4 --pix_fmt yuv420p10le
+    python rs.py --model ck.pt --src clip8.y4m --save_dir out10.y4m --out_depth 10
 """
 from __future__ import annotations
 
@@ -49,7 +58,7 @@ from image_super_resolution_amd import checkpoint, models, tiler, video
 VID_FORMATS = video.VID_FORMATS
 RAW_FORMATS = video.RGB_FORMATS
 YUV_FORMATS = video.YUV_FORMATS
-YUV_OUT = {".y4m": "yuv420p", ".yuv": "yuv420p", ".nv12": "nv12"}  # save_dir suffix -> pix_fmt
+YUV_OUT = {".y4m": "yuv420p", ".yuv": "yuv420p", ".nv12": "nv12"}  # save_dir suffix -> pix_fmt (at 8 bits)
 
 
 def read_image(path: Path) -> torch.Tensor:
@@ -96,13 +105,15 @@ def compare_with_ref(out: torch.Tensor, ref: torch.Tensor, ref_path: Path, borde
 def video_formats(kw, source, result: Path):
     """(pix_fmt_in, yuv_in, pix_fmt_out, yuv_out) of a video run.  The input's format is the source's
     (a .y4m header's siting and range, unless a --yuv_* flag is given); the output's follows the
-    save_dir suffix, for a container --pix_fmt, and inherits the input's siting and range."""
+    save_dir suffix, for a container --pix_fmt, and inherits the input's siting, range and depth;
+    --out_depth sets the output's depth apart (rgb24 input counts as 8 bits).  A 10-bit .y4m has no tag for
+    center siting: without --yuv_siting such an output is left-sited."""
     flags = {k: kw.get(f"yuv_{k}") for k in ("matrix", "range", "siting")}
 
     def with_flags(fmt: video.YUVFormat) -> video.YUVFormat:
         return video.YUVFormat(fmt.layout, flags["matrix"] or fmt.matrix,
                                fmt.full_range if flags["range"] is None else flags["range"] == "full",
-                               flags["siting"] or fmt.siting)
+                               flags["siting"] or fmt.siting, fmt.depth)
 
     yuv_in = getattr(source, "yuv", None)
     pix_in = "rgb24" if yuv_in is None else source.pix_fmt
@@ -118,7 +129,13 @@ def video_formats(kw, source, result: Path):
     yuv_out = None
     if pix_out != "bgr24":
         like = yuv_in or video.YUVFormat()
-        yuv_out = with_flags(video.YUVFormat(video.yuvmod.PIX_FMTS[pix_out], "auto", like.full_range, like.siting))
+        # a file of frames inherits the input's depth; a container follows --pix_fmt
+        depth = kw.get("out_depth") or (like.depth if suffix in YUV_OUT else video.yuvmod.PIX_FMT_DEPTH[pix_out])
+        siting = like.siting
+        if depth == 10 and suffix == ".y4m" and flags["siting"] is None:
+            siting = "left"
+        yuv_out = with_flags(video.YUVFormat(video.yuvmod.PIX_FMTS[pix_out], "auto", like.full_range, siting, depth))
+        pix_out = yuv_out.pix_fmt
     return pix_in, yuv_in, pix_out, yuv_out
 
 
@@ -224,10 +241,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ref", type=str, default="", help="ground-truth image of the output's size: after the still "
                    "is written, print one JSON line with its PSNR / PSNR-Y / SSIM-Y against it (image branch)")
     p.add_argument("--ref_border", type=int, default=4, help="pixels cropped from every side before the metrics")
-    p.add_argument("--pix_fmt", choices=("rgb24", "yuv420p", "nv12"), default="rgb24",
+    p.add_argument("--pix_fmt", choices=("rgb24", "yuv420p", "nv12", "yuv420p10le", "p010le"), default="rgb24",
                    help="video through ffmpeg: the frames piped from the decoder and to the encoder (rgb24: rgb24 in, "
-                        "bgr24 out; yuv420p / nv12: 8-bit 4:2:0 both ways, colour conversion on the GPU).  .y4m / .yuv / "
-                        ".i420 / .nv12 sources and save_dirs carry their own format")
+                        "bgr24 out; yuv420p / nv12: 8-bit 4:2:0 both ways, yuv420p10le / p010le: 10-bit, colour "
+                        "conversion on the GPU).  .y4m / .yuv / .i420 / .nv12 sources and save_dirs carry their own "
+                        "layout; for a raw .yuv / .i420 / .nv12 source a 10-bit name says it holds 16-bit words")
+    p.add_argument("--out_depth", type=int, choices=(8, 10), default=None,
+                   help="4:2:0 output: bits per sample (default: the input's; rgb24 input counts as 8)")
     p.add_argument("--yuv_matrix", choices=("auto", "bt601", "bt709"), default=None,
                    help="4:2:0 frames: the matrix (default auto: bt709 at a height of 720 or more, else bt601)")
     p.add_argument("--yuv_range", choices=("limited", "full"), default=None,
