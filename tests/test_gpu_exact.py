@@ -12,8 +12,9 @@ the CPU in tests/test_exact_ref_cpu.py.  The sign of zero is not pinned (torch.e
 
 Grids: 7x5 (inside one 16 x 32 tile), 16x32 (one tile), 17x33 with n = 2 (one row and one column
 past a tile, plus the image stride).  The 9x9 tail forward (tanh) has its own file,
-test_gpu_tail_exact.py: exact pre-activations, a derived bracket for tanhf.  Out of scope: BatchNorm,
-the optimiser and the persistent trunk (its slopes are no powers of two; it is pinned bitwise to the
+test_gpu_tail_exact.py: exact pre-activations, a derived bracket for tanhf; so have the train-mode BatchNorm kernels,
+test_gpu_bn_exact.py (each stage from hand-set dyadic statistics), and the optimiser kernels,
+test_gpu_optim_exact.py.  Out of scope: the persistent trunk (its slopes are no powers of two; it is pinned bitwise to the
 per-conv launches in test_gpu_chain.py)."""
 import ctypes
 import functools
