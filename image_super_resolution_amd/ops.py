@@ -6,8 +6,6 @@ CUDA (HIP) tensors and raise otherwise.
 """
 from __future__ import annotations
 
-import os as _os
-
 import ctypes
 from dataclasses import dataclass
 
@@ -413,23 +411,20 @@ def wgrad3x3_desc(x: ActBuffer, cin: int, g: ActBuffer, cout: int, dw: torch.Ten
     return d
 
 
-_WGRAD_VARIANT = int(_os.environ.get("ISR_WGRAD_VARIANT", "0"))  # A/B only (isr_wgrad3x3_variant)
+def _launch_wgrad(entry: str, d, device) -> None:
+    """Size the split-K workspace (`<entry>_workspace_bytes`; 0: none, or a refusal the entry
+    point reports itself) and launch `entry` on the current stream."""
+    lib = _lib.load()
+    nbytes = getattr(lib, entry + "_workspace_bytes")(ctypes.byref(d))
+    ws = (None, 0)
+    if nbytes:
+        t = _WS.get(nbytes, device)
+        ws = (t.data_ptr(), t.numel())
+    check(getattr(lib, entry)(ctypes.byref(d), *ws, _stream()), entry)
 
 
 def launch_wgrad3x3(d: IsrWgradDesc, device) -> None:
-    lib = _lib.load()
-    if _WGRAD_VARIANT:
-        nbytes = lib.isr_wgrad3x3_variant_workspace_bytes(ctypes.byref(d), _WGRAD_VARIANT)
-        ws = _WS.get(max(nbytes, 16), device)
-        check(lib.isr_wgrad3x3_variant(ctypes.byref(d), _WGRAD_VARIANT, ws.data_ptr(), ws.numel(), _stream()),
-              "isr_wgrad3x3_variant")
-        return
-    nbytes = lib.isr_wgrad3x3_workspace_bytes(ctypes.byref(d))
-    if nbytes == 0:
-        check(lib.isr_wgrad3x3(ctypes.byref(d), None, 0, _stream()), "isr_wgrad3x3")
-        return
-    ws = _WS.get(nbytes, device)
-    check(lib.isr_wgrad3x3(ctypes.byref(d), ws.data_ptr(), ws.numel(), _stream()), "isr_wgrad3x3")
+    _launch_wgrad("isr_wgrad3x3", d, device)
 
 
 def wgrad3x3(x: ActBuffer, cin: int, g: ActBuffer, cout: int, dw: torch.Tensor, db: torch.Tensor | None = None,
@@ -463,13 +458,7 @@ def wgrad9x9_desc(p: torch.Tensor, q: ActBuffer, dw: torch.Tensor, db: torch.Ten
 
 
 def launch_wgrad9x9(d: IsrWgrad9Desc, device) -> None:
-    lib = _lib.load()
-    nbytes = lib.isr_wgrad9x9_workspace_bytes(ctypes.byref(d))
-    if nbytes == 0:
-        check(lib.isr_wgrad9x9(ctypes.byref(d), None, 0, _stream()), "isr_wgrad9x9")
-        return
-    ws = _WS.get(nbytes, device)
-    check(lib.isr_wgrad9x9(ctypes.byref(d), ws.data_ptr(), ws.numel(), _stream()), "isr_wgrad9x9")
+    _launch_wgrad("isr_wgrad9x9", d, device)
 
 
 def wgrad9x9(p: torch.Tensor, q: ActBuffer, dw: torch.Tensor, db: torch.Tensor | None = None, **kw) -> None:

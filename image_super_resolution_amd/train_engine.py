@@ -31,6 +31,8 @@ from __future__ import annotations
 import os as _os
 
 import ctypes
+from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -42,6 +44,49 @@ from .ops import ActBuffer
 from .train_layers import TrainConv
 
 LEAKY = 0.01
+
+
+@dataclass
+class Step:
+    """One entry of a plan's launch program (`fwd_launches` / `bwd_launches`).
+
+    kind     forward:  "head" | "conv" | "chain" | "bnf" | "tail"
+             backward: "wg9" | "head" | "wg3" | "wg3g" | "conv" | "bchain" | "bnb" | "ew", and the
+             stream markers "ready" | "evrec" | "evwait" (no launch)
+    desc     the launch's descriptor ("wg3g": the descriptor array)
+    conv     index into `plan.convs` of the layer whose gradient offsets are patched into `desc`
+             per call ("wg3g": one index per descriptor)
+    side     the launch runs — a "ready" segment completes — on the side stream when there is one
+    bn_state the BatchNorm layer's scratch ("bnf" / "bnb": its accumulators are zeroed per call)
+    gather   a "conv" that is an RDB gather conv (what the persistent backward chain replaces)
+    id       "ready": the gradient segment; "evrec" / "evwait": the event"""
+    kind: str
+    desc: object = None
+    conv: int | list[int] | None = None
+    side: bool = False
+    bn_state: ops.BNState | None = None
+    gather: bool = False
+    id: int | str | None = None
+
+
+class _Options(NamedTuple):
+    chain: bool      # ISR_TRAIN_CHAIN (1): the trunk forward on the persistent trunk kernel
+    gather: bool     # ISR_TRAIN_GATHER (1): the gather walk (never with BatchNorm)
+    side: bool       # ISR_TRAIN_SIDE (1): the gather walk's weight gradients on a second stream
+    wg_group: bool   # ISR_TRAIN_WG_GROUP (1): an RDB's side weight gradients as one grouped launch
+    bwd_chain: bool  # ISR_TRAIN_BWD_CHAIN (0): the gather convs on the persistent trunk kernel
+
+
+def _options(has_bn: bool) -> _Options:
+    """The plan's switches, read when a plan is built."""
+    def on(name: str, default: str) -> bool:
+        return _os.environ.get("ISR_TRAIN_" + name, default) == "1"
+
+    persistent = not _device_shared()
+    gather = not has_bn and on("GATHER", "1")
+    return _Options(chain=not has_bn and on("CHAIN", "1") and persistent, gather=gather,
+                    side=gather and on("SIDE", "1"), wg_group=on("WG_GROUP", "1"),
+                    bwd_chain=gather and on("BWD_CHAIN", "0") and persistent)
 
 
 def _generator_convs(gen: nn.Module) -> tuple[TrainConv, list[list[TrainConv]], TrainConv, list[TrainConv], TrainConv]:
@@ -99,12 +144,16 @@ class GeneratorTrainPlan:
             hh, ww, ha, wa = 2 * hh, 2 * ww, 2 * ha, 2 * wa
             self.ups.append(ActBuffer.alloc(n, hh, ww, 64, 4 if s == S - 1 else 1, dev, ha=ha, wa=wa))
         self.out_shape = (n, 3, hh, ww)
+        self.dummy_x = torch.empty(n, 3, h, w, device=dev)
+        self.dummy_y = torch.empty(self.out_shape, device=dev)
         # ---- gradients
         self.G = [ActBuffer.alloc(n, h, w, 192, 1, dev) for _ in range(3)]
         self.gT = ActBuffer.alloc(n, h, w, 64, 1, dev)
         self.gups = [ActBuffer.alloc(u.n, u.h, u.w, 64, 2, dev, ha=u.ha, wa=u.wa) for u in self.ups]
         self.gf0 = ActBuffer.alloc(n, h, w, 64, 1, dev)
+        self.gp = torch.empty(self.out_shape, device=dev)
         self.convs = [self.head] + [c for r in self.rdbs for c in r] + [self.conv1] + self.scalers + [self.tail]
+        self._conv_index = {id(c): i for i, c in enumerate(self.convs)}
         # ---- train-mode BatchNorm (ResNet): pre-BN conv outputs z and per-layer BN scratch
         self.has_bn = any(c.bn is not None for c in self.convs)
         if self.has_bn:
@@ -116,22 +165,15 @@ class GeneratorTrainPlan:
                     c.bn_state = ops.BNState(c.cout, dev)
         self.bn_counters = [c.bn.num_batches_tracked for c in self.convs
                             if c.bn is not None and c.bn.num_batches_tracked is not None]
-        # ---- parameters / gradient layout (one flat fp32 gradient buffer per backward)
-        self._params, self._goff = [], []
-        off = 0
-        for c in self.convs:
-            for p in c.params():
-                self._params.append(p)
-                self._goff.append(off)
-                off += (p.numel() + 3) // 4 * 4  # 16-byte aligned views
-        self._gsize = off
+        self._layout_gradients()
+        opt = _options(self.has_bn)
         # RDB input gradients as "gather" convs (no BatchNorm): per RDB, one conv per dense-buffer
         # block — the gradient of block o_t (and of x) is ONE conv over the concatenated output
         # gradients of every conv that read it (forward-shaped: K 576..1728, 32 / 64 outputs,
         # each output written once) instead of an accumulate-into-all-channels transposed conv
         # per layer (K 288, read-modify-write of 64..192 channels).  Weights: slices of the
         # layers' transposed weights, packed per step by the same batched launch.
-        self.gather = (not self.has_bn) and _os.environ.get("ISR_TRAIN_GATHER", "1") == "1"
+        self.gather = opt.gather
         if self.gather:
             nbytes = self.lib.isr_conv3x3_packed_bytes
             self.gpacks = []
@@ -140,12 +182,46 @@ class GeneratorTrainPlan:
                       for t in range(4)}
                 gp["x"] = torch.empty(nbytes(64, 192) // 2, dtype=torch.bfloat16, device=dev)
                 self.gpacks.append(gp)
+            # one gradient dense buffer per RDB, E_j = [g_out | g_3 | g_2 | g_1 | g_0] (the gather
+            # walk), and the trunk's input gradient (192 channels, 64 used: the persistent backward
+            # chain needs one buffer geometry)
+            self.Eg = [ActBuffer.alloc(n, h, w, 192, 1, dev) for _ in range(nr)]
+            self.gtrunk = ActBuffer.alloc(n, h, w, 192, 1, dev)
         self.pack()
-        self._build()
+        self.fwd_launches = self._build_forward(opt)
+        self.bwd_launches = self._build_backward(opt)
+        self._size_workspaces(opt)
 
     # ------------------------------------------------------------------ setup
     def params(self) -> list[torch.Tensor]:
         return list(self._params)
+
+    def _layout_gradients(self) -> None:
+        """One flat fp32 gradient buffer per backward: `_goff` per parameter (the order of
+        params()), `_conv_goff` per conv as (w, b or None, bn weight or None, bn bias or None),
+        and the data-parallel segments."""
+        self._params, self._goff, self._conv_goff = [], [], []
+        off = 0
+        for c in self.convs:
+            offs = []
+            for p in c.params():
+                self._params.append(p)
+                offs.append(off)
+                off += (p.numel() + 3) // 4 * 4  # 16-byte aligned views
+            self._goff += offs
+            wo, rest = offs[0], offs[1:]
+            bo = rest.pop(0) if c.b is not None else None
+            self._conv_goff.append((wo, bo, *(rest if c.bn is not None else (None, None))))
+        self._gsize = off
+        # data-parallel gradient buckets (SURVEY.md §8e): the flat buffer in backward order is
+        # [conv1 .. tail] (end of the buffer), RRDB nb-1, ..., RRDB 0, head (start) — contiguous
+        # descending ranges, each complete at its "ready" step of the backward list
+        first = lambda conv_index: self._conv_goff[conv_index][0]
+        nr = len(self.rdbs)
+        seg = {"tail": (first(1 + 5 * nr), self._gsize), "head": (0, first(1) if nr else self._gsize)}
+        for i in range(nr // 3):
+            seg[i] = (first(1 + 15 * i), first(1 + 15 * (i + 1)))
+        self._segments = seg
 
     def pack(self) -> None:
         """Refresh the packed bf16 weights from the fp32 parameters (every step):
@@ -196,138 +272,145 @@ class GeneratorTrainPlan:
                     items.append((cs[k].w, out, 32, co, True, False, sx, n0, cs[k].cin, (off // 16) * 9 * co * 16))
         return items
 
-    def _build(self):
-        a, lib = self.a, self.lib
-        conv, head, tail = lib.isr_conv3x3_fwd, lib.isr_head9x9_fwd, lib.isr_tail9x9_fwd
-        D, f0, T = self.D, self.f0, self.T
-        self.dummy_x = torch.empty(self.out_shape[0], 3, f0.h, f0.w, device=self.device)
-        self.dummy_y = torch.empty(self.out_shape, device=self.device)
-        F = []
-        self.head_desc = ops.head9x9_desc(self.dummy_x, self.head.fwd, self.head.bias, f0, slope=self.slope0, y2=D[0])
-        F.append((head, self.head_desc))
-        def conv_bn(x, cin, c, y, y_coff, z, z_coff, slope, **res):
-            """conv → y directly, or (BN layer) conv → z, batch stats, BN+act(+residuals) → y."""
-            if c.bn is None:
-                F.append((conv, ops.conv3x3_desc(x, cin, c.fwd, c.bias, c.cout, y, y_coff=y_coff, slope=slope, **res)))
-            else:
-                F.append((conv, ops.conv3x3_desc(x, cin, c.fwd, c.bias, c.cout, z, y_coff=z_coff, slope=1.0)))
-                F.append(("bnf", ops.bn_desc(z, y, c.cout, c.bn_state, c.bn, z_coff=z_coff, y_coff=y_coff,
-                                             slope=slope, **res), c.bn_state))
+    # ---------------------------------------------------------------- forward program
+    def _conv_bn(self, x, cin, c, y, y_coff, z, z_coff, slope, **res) -> list[Step]:
+        """conv → y directly, or (BN layer) conv → z, batch stats, BN+act(+residuals) → y."""
+        if c.bn is None:
+            return [Step("conv", ops.conv3x3_desc(x, cin, c.fwd, c.bias, c.cout, y, y_coff=y_coff, slope=slope, **res))]
+        return [Step("conv", ops.conv3x3_desc(x, cin, c.fwd, c.bias, c.cout, z, y_coff=z_coff, slope=1.0)),
+                Step("bnf", ops.bn_desc(z, y, c.cout, c.bn_state, c.bn, z_coff=z_coff, y_coff=y_coff, slope=slope,
+                                        **res), bn_state=c.bn_state)]
 
-        trunk0 = len(F)
+    def _build_forward(self, opt: _Options) -> list[Step]:
+        D, f0, T = self.D, self.f0, self.T
+        self.head_desc = ops.head9x9_desc(self.dummy_x, self.head.fwd, self.head.bias, f0, slope=self.slope0, y2=D[0])
+        F = [Step("head", self.head_desc)] + self._forward_trunk(opt)
+        F += self._conv_bn(D[-1], 64, self.conv1, T, 0, self.Tz if self.has_bn else None, 0, 1.0, r1=f0, s1=1.0)
+        cur = T
+        for s, c in enumerate(self.scalers):
+            F.append(Step("conv", ops.conv3x3_desc(cur, 64, c.fwd, c.bias, 256, self.ups[s], slope=LEAKY, shuffle=2)))
+            cur = self.ups[s]
+        self.tail_desc = ops.tail9x9_desc(cur, self.tail.fwd, self.tail.bias, self.dummy_y)
+        F.append(Step("tail", self.tail_desc))
+        return F
+
+    def _forward_trunk(self, opt: _Options) -> list[Step]:
+        """The RDBs' convs, each RDB in its own dense buffer; without BatchNorm the whole trunk
+        as ONE persistent isr_conv_chain launch (as inference, engine.ConvChain)."""
+        a, D = self.a, self.D
+        F = []
         for j, cs in enumerate(self.rdbs):
             Zj = self.Zb[j] if self.has_bn else None
-            for k in range(4):
-                c = cs[k]
-                conv_bn(D[j], c.cin, c, D[j], c.cin, Zj, c.cin, LEAKY)
-            c = cs[4]
+            for c in cs[:4]:
+                F += self._conv_bn(D[j], c.cin, c, D[j], c.cin, Zj, c.cin, LEAKY)
             extra = dict(r2=D[j - 2], s2=a) if j % 3 == 2 else {}
-            conv_bn(D[j], 192, c, D[j + 1], 0, Zj, 0, 1.0, r1=D[j], s1=a, **extra)
+            F += self._conv_bn(D[j], 192, cs[4], D[j + 1], 0, Zj, 0, 1.0, r1=D[j], s1=a, **extra)
         self.chain = None
-        if not self.has_bn and self.rdbs and _os.environ.get("ISR_TRAIN_CHAIN", "1") == "1" and not _device_shared():
-            # no BatchNorm: the whole trunk forward as ONE persistent isr_conv_chain launch (as
-            # inference, engine.ConvChain); every RDB writes its own dense buffer here
-            from .engine import ConvChain
+        if opt.chain and self.rdbs:
+            from .engine import CHAIN_ACQUIRE, ConvChain
             try:
-                from .engine import CHAIN_ACQUIRE
-                self.chain = ConvChain([e[1] for e in F[trunk0:]], D[0], self.device, acquire=CHAIN_ACQUIRE)
+                self.chain = ConvChain([s.desc for s in F], D[0], self.device, acquire=CHAIN_ACQUIRE)
             except ValueError as e:  # not silent: the per-conv trunk costs ~3.5 ms per SRGAN step
                 import warnings
                 warnings.warn(f"training trunk runs per conv (persistent trunk kernel refused the layers: {e})")
-                self.chain = None
-            if self.chain is not None:
-                F[trunk0:] = [(self.chain.fn, self.chain.desc)]
-        c = self.conv1
-        conv_bn(D[-1], 64, c, T, 0, self.Tz if self.has_bn else None, 0, 1.0, r1=f0, s1=1.0)
-        cur = T
-        for s, c in enumerate(self.scalers):
-            F.append((conv, ops.conv3x3_desc(cur, 64, c.fwd, c.bias, 256, self.ups[s], slope=LEAKY, shuffle=2)))
-            cur = self.ups[s]
-        self.tail_desc = ops.tail9x9_desc(cur, self.tail.fwd, self.tail.bias, self.dummy_y)
-        F.append((tail, self.tail_desc))
-        self.fwd_launches = F
+            else:
+                F = [Step("chain", self.chain.desc)]
+        return F
 
-        # ---- backward.  Entries: ("conv", desc) | ("wg3", desc, conv_index) | ("wg9", desc, conv_index)
-        #      | ("head", desc) | ("ew", desc).  dw/db pointers are patched per call.
-        B = []
-        ci = {id(c): i for i, c in enumerate(self.convs)}
-        dev = self.device
+    # --------------------------------------------------------------- backward program
+    def _wg3(self, x, cin, g, cout, c, *, side=False, **kw) -> Step:
+        """3x3 weight gradient of conv c; dw / db are patched per call (placeholders here)."""
+        d = ops.wgrad3x3_desc(x, cin, g, cout, _meta_dw(cout, cin, 3, self.device), None, **kw)
+        return Step("wg3", d, conv=self._conv_index[id(c)], side=side)
 
-        def wg3(x, cin, g, cout, c, *, x_coff=0, g_coff=0, scale=1.0, g_sub2=False, side=False):
-            d = ops.wgrad3x3_desc(x, cin, g, cout, _meta_dw(cout, cin, 3, dev), None, x_coff=x_coff, g_coff=g_coff,
-                                  scale=scale, g_sub2=g_sub2)
-            B.append(("wg3", d, ci[id(c)], side))
+    def _bn_bwd(self, c, z, g, **kw) -> Step:
+        """BN input gradient of conv c: g (gradient wrt the BN output) → dz (in place if dz is None)."""
+        return Step("bnb", ops.bn_desc(z, g, c.cout, c.bn_state, c.bn, **kw), conv=self._conv_index[id(c)],
+                    bn_state=c.bn_state)
 
-        # tail
-        self.gp = torch.empty(self.out_shape, device=dev)
+    def _build_backward(self, opt: _Options) -> list[Step]:
+        if self.gather:
+            # conv1's input gradient (g_R of the last RRDB) goes straight into E_{nr-1}[0:64]
+            B = self._backward_upsampler(self.Eg[-1]) + self._gather_walk()
+            g_trunk = self.gtrunk
+        else:
+            walk, g_trunk = self._rotating_walk()
+            B = self._backward_upsampler(self.G[0]) + walk
+        B += self._backward_trunk_end(g_trunk)
+        self.bchain = None
+        if opt.bwd_chain:
+            B = self._backward_chain(B)
+        if opt.wg_group:
+            B = _group_side_wgrads(B, self.lib)
+        return B
+
+    def _backward_upsampler(self, g_last: ActBuffer) -> list[Step]:
+        """Tail, Scalers (reverse) and conv1; conv1's input gradient (g_R of the last RRDB)
+        goes into g_last[0:64]."""
+        D, T = self.D, self.T
         ut = self.ups[-1]
-        d9 = ops.wgrad9x9_desc(self.gp, ut, _meta_dw(3, 64, 9, dev), None, head=False)
-        B.append(("wg9", d9, ci[id(self.tail)]))
-        B.append(("head", ops.head9x9_desc(self.gp, self.tail.bwd, None, self.gups[-1], slope=1.0, m=ut,
-                                           mslope=LEAKY)))
-        # scalers (reverse)
+        d9 = ops.wgrad9x9_desc(self.gp, ut, _meta_dw(3, 64, 9, self.device), None, head=False)
+        B = [Step("wg9", d9, conv=self._conv_index[id(self.tail)]),
+             Step("head", ops.head9x9_desc(self.gp, self.tail.bwd, None, self.gups[-1], slope=1.0, m=ut,
+                                           mslope=LEAKY))]
         for s in range(len(self.scalers) - 1, -1, -1):
             c = self.scalers[s]
             xin = self.ups[s - 1] if s > 0 else T
-            wg3(xin, 64, self.gups[s], 256, c, g_sub2=True)
+            B.append(self._wg3(xin, 64, self.gups[s], 256, c, g_sub2=True))
             out = self.gups[s - 1] if s > 0 else self.gT
             kw = dict(m=self.ups[s - 1], mslope=LEAKY) if s > 0 else {}
-            B.append(("conv", ops.conv3x3_desc(self.gups[s], 256, c.bwd, None, 64, out, x_sub2=True, **kw)))
-        def bn_bwd(c, z, g, *, z_coff=0, g_coff=0, dz=None, gscale=1.0):
-            """BN input gradient of conv c: g (gradient wrt the BN output) → dz (in place if dz is None)."""
-            B.append(("bnb", ops.bn_desc(z, g, c.cout, c.bn_state, c.bn, z_coff=z_coff, y_coff=g_coff, dz=dz,
-                                         gscale=gscale), ci[id(c)], c.bn_state))
-
+            B.append(Step("conv", ops.conv3x3_desc(self.gups[s], 256, c.bwd, None, 64, out, x_sub2=True, **kw)))
         # conv1:  T = BN?(conv1(D[-1][0:64])) + f0
         c = self.conv1
-        U, V, W = self.G
         g1 = self.gT
         if c.bn is not None:
-            bn_bwd(c, self.Tz, self.gT, dz=self.gtmp)
+            B.append(self._bn_bwd(c, self.Tz, self.gT, dz=self.gtmp))
             g1 = self.gtmp
-        wg3(D[-1], 64, g1, 64, c)
-        B.append(("ready", "tail", False))  # conv1 / Scaler / tail gradients complete (main stream)
-        B.append(("conv", ops.conv3x3_desc(g1, 64, c.bwd, None, 64, U)))
-        # RRDBs, reverse
-        nb = len(self.rdbs) // 3
-        if self.gather:
-            # gather form (no BN): one gradient dense buffer per RDB, E_j = [g_out | g_3 | g_2 |
-            # g_1 | g_0]; g_out (the RDB output gradient) arrives in E_j[0:64], each target conv
-            # appends its block, the x target writes the RDB input gradient into E_{j-1}[0:64]
-            # (RDB 0: into `self.gtrunk`).  Nothing is overwritten, so the five weight gradients
-            # of RDB j run on a second HIP stream (`side`) as soon as its target 0 is done
-            # ("evrec" / "evwait"), beside the next RDBs' gather convs.
-            nr = len(self.rdbs)
-            self.Eg = [ActBuffer.alloc(n_, h_, w_, 192, 1, dev) for n_, h_, w_ in [(D[0].n, D[0].h, D[0].w)] * nr]
-            # 192 channels (64 used): the persistent backward chain needs one buffer geometry
-            self.gtrunk = ActBuffer.alloc(D[0].n, D[0].h, D[0].w, 192, 1, dev)
-            # conv1's input gradient (g_R of the last RRDB) goes straight into E_{nr-1}[0:64]
-            B[-1] = ("conv", ops.conv3x3_desc(g1, 64, c.bwd, None, 64, self.Eg[nr - 1]))
-            for i in range(nb - 1, -1, -1):
-                for step, j in enumerate((3 * i + 2, 3 * i + 1, 3 * i)):
-                    cs, Dj, gp, E = self.rdbs[j], D[j], self.gpacks[j], self.Eg[j]
-                    gout = self.Eg[j - 1] if j > 0 else self.gtrunk
-                    res = a if step == 0 else 1.0
-                    for t in range(3, -1, -1):
-                        slot = 64 + 32 * (3 - t)
-                        B.append(("conv", ops.conv3x3_desc(E, slot, gp[t], None, 32, E, y_coff=slot, m=Dj,
-                                                           m_coff=64 + 32 * t, m_c0=0, mslope=LEAKY), "gather"))
-                    B.append(("evrec", j))
-                    B.append(("evwait", j))
-                    wg3(Dj, 192, E, 64, cs[4], scale=a * res, side=True)
-                    for t in range(3, -1, -1):
-                        wg3(Dj, cs[t].cin, E, 32, cs[t], g_coff=64 + 32 * (3 - t), side=True)
-                    if step == 2:  # RRDB i's weight gradients are all enqueued (side stream)
-                        B.append(("ready", i, True))
-                    # v = (acc' + g_out) * res (+ g_R: the RRDB's own residual, first RDB); the pack
-                    # carries 1 / res, so acc' = acc / res
-                    kw = dict(r2=self.Eg[3 * i + 2]) if step == 2 else {}
-                    # r1_cn=64 (= every output channel, the same sums) keeps the per-conv launch on the
-                    # plain 192->64 kernel; the persistent backward chain folds r1 (r1_cn = 0)
-                    B.append(("conv", ops.conv3x3_desc(E, 192, gp["x"], None, 64, gout, r1=E, s1=1.0, s2=res,
-                                                       r1_cn=64, **kw), "gather"))
-            U = self.gtrunk
-        for i in range(nb - 1, -1, -1) if not self.gather else ():
+        B.append(self._wg3(D[-1], 64, g1, 64, c))
+        B.append(Step("ready", id="tail"))  # conv1 / Scaler / tail gradients complete (main stream)
+        B.append(Step("conv", ops.conv3x3_desc(g1, 64, c.bwd, None, 64, g_last)))
+        return B
+
+    def _gather_walk(self) -> list[Step]:
+        """RRDBs in reverse, gather form (no BN): g_out (the RDB output gradient) arrives in
+        E_j[0:64], each target conv appends its block, the x target writes the RDB input gradient
+        into E_{j-1}[0:64] (RDB 0: into `self.gtrunk`).  Nothing is overwritten, so the five
+        weight gradients of RDB j run on a second HIP stream (`side`) as soon as its target 0 is
+        done ("evrec" / "evwait"), beside the next RDBs' gather convs."""
+        a, D = self.a, self.D
+        B = []
+        for i in range(len(self.rdbs) // 3 - 1, -1, -1):
+            for step, j in enumerate((3 * i + 2, 3 * i + 1, 3 * i)):
+                cs, Dj, gp, E = self.rdbs[j], D[j], self.gpacks[j], self.Eg[j]
+                gout = self.Eg[j - 1] if j > 0 else self.gtrunk
+                res = a if step == 0 else 1.0
+                for t in range(3, -1, -1):
+                    slot = 64 + 32 * (3 - t)
+                    B.append(Step("conv", ops.conv3x3_desc(E, slot, gp[t], None, 32, E, y_coff=slot, m=Dj,
+                                                           m_coff=64 + 32 * t, m_c0=0, mslope=LEAKY), gather=True))
+                B += [Step("evrec", id=j), Step("evwait", id=j)]
+                B.append(self._wg3(Dj, 192, E, 64, cs[4], scale=a * res, side=True))
+                for t in range(3, -1, -1):
+                    B.append(self._wg3(Dj, cs[t].cin, E, 32, cs[t], g_coff=64 + 32 * (3 - t), side=True))
+                if step == 2:  # RRDB i's weight gradients are all enqueued (side stream)
+                    B.append(Step("ready", id=i, side=True))
+                # v = (acc' + g_out) * res (+ g_R: the RRDB's own residual, first RDB); the pack
+                # carries 1 / res, so acc' = acc / res
+                kw = dict(r2=self.Eg[3 * i + 2]) if step == 2 else {}
+                # r1_cn=64 (= every output channel, the same sums) keeps the per-conv launch on the
+                # plain 192->64 kernel; the persistent backward chain folds r1 (r1_cn = 0)
+                B.append(Step("conv", ops.conv3x3_desc(E, 192, gp["x"], None, 64, gout, r1=E, s1=1.0, s2=res,
+                                                       r1_cn=64, **kw), gather=True))
+        return B
+
+    def _rotating_walk(self) -> tuple[list[Step], ActBuffer]:
+        """RRDBs in reverse over the three rotating gradient buffers (BatchNorm models, or
+        ISR_TRAIN_GATHER=0); returns the steps and the buffer whose [0:64) holds the trunk's
+        input gradient."""
+        a, D = self.a, self.D
+        U, V, W = self.G
+        B = []
+        for i in range(len(self.rdbs) // 3 - 1, -1, -1):
             # g_R (gradient wrt the RRDB output) is in U[0:64]
             seq = [(3 * i + 2, U, V), (3 * i + 1, V, W), (3 * i, W, V)]
             for step, (j, gin, gout) in enumerate(seq):
@@ -338,102 +421,39 @@ class GeneratorTrainPlan:
                 # final conv: out = conv*a + Dj[0:64]  (third RDB: (...)*a + RRDB input)
                 res = a if last_rdb else 1.0       # coefficient of Dj[0:64] in the RRDB output
                 if c5.bn is None:
-                    wg3(Dj, 192, gin, 64, c5, scale=(a * a if last_rdb else a))
-                    B.append(("conv", ops.conv3x3_desc(gin, 64, c5.bwd, None, 192, gout, r1=gin, r1_cn=64,
-                                                       s2=res, m=Dj, m_c0=160, mslope=LEAKY)))
+                    B.append(self._wg3(Dj, 192, gin, 64, c5, scale=(a * a if last_rdb else a)))
+                    B.append(Step("conv", ops.conv3x3_desc(gin, 64, c5.bwd, None, 192, gout, r1=gin, r1_cn=64,
+                                                           s2=res, m=Dj, m_c0=160, mslope=LEAKY)))
                 else:
                     # dz5 = BN'(a*res * g_R) into gtmp; residual keeps g_R: y = (v/res + g_R) * res
-                    bn_bwd(c5, self.Zb[j], gin, dz=self.gtmp, gscale=a * res)
-                    wg3(Dj, 192, self.gtmp, 64, c5)
-                    B.append(("conv", ops.conv3x3_desc(self.gtmp, 64, c5.bwd, None, 192, gout, r1=gin, r1_cn=64,
-                                                       s1=1.0 / res, s2=res, m=Dj, m_c0=160, mslope=LEAKY)))
+                    B.append(self._bn_bwd(c5, self.Zb[j], gin, dz=self.gtmp, gscale=a * res))
+                    B.append(self._wg3(Dj, 192, self.gtmp, 64, c5))
+                    B.append(Step("conv", ops.conv3x3_desc(self.gtmp, 64, c5.bwd, None, 192, gout, r1=gin, r1_cn=64,
+                                                           s1=1.0 / res, s2=res, m=Dj, m_c0=160, mslope=LEAKY)))
                 for k in range(3, -1, -1):
                     ck = cs[k]
                     slot = 64 + 32 * k
                     if ck.bn is not None:  # slot k is complete and LeakyReLU'-masked: BN backward in place
-                        bn_bwd(ck, self.Zb[j], gout, z_coff=slot, g_coff=slot)
-                    wg3(Dj, ck.cin, gout, 32, ck, g_coff=slot)
+                        B.append(self._bn_bwd(ck, self.Zb[j], gout, z_coff=slot, y_coff=slot))
+                    B.append(self._wg3(Dj, ck.cin, gout, 32, ck, g_coff=slot))
                     kw = dict(m=Dj, m_c0=slot - 32, mslope=LEAKY) if k > 0 else {}
                     if k == 0 and step == 2:
                         kw = dict(r2=U, s2=1.0)  # + g_R: the RRDB's own residual
-                    B.append(("conv", ops.conv3x3_desc(gout, 32, ck.bwd, None, ck.cin, gout, x_coff=slot,
-                                                       r1=gout, **kw)))
-            B.append(("ready", i, False))  # RRDB i's gradients complete (main stream)
+                    B.append(Step("conv", ops.conv3x3_desc(gout, 32, ck.bwd, None, ck.cin, gout, x_coff=slot,
+                                                           r1=gout, **kw)))
+            B.append(Step("ready", id=i))  # RRDB i's gradients complete (main stream)
             # RRDB input gradient now in V[0:64]; rotate so it becomes the next g_R
             U, V, W = V, W, U
-        # trunk: g_f0 = chain + g_T, then LeakyReLU'(f0) of conv0
-        B.append(("ew", ops.ew_combine_desc(self.gf0, U, 64, sa=1.0, b=self.gT, sb=1.0, m=f0,
-                                            mslope=self.slope0)))
-        d9h = ops.wgrad9x9_desc(self.dummy_x, self.gf0, _meta_dw(64, 3, 9, dev), None, head=True)
-        B.append(("wg9", d9h, ci[id(self.head)]))
-        B.append(("ready", "head", False))
-        self.bchain = None
-        if self.gather and _os.environ.get("ISR_TRAIN_BWD_CHAIN", "0") == "1" and not _device_shared():
-            B = self._backward_chain(B)
-        wg_group = _os.environ.get("ISR_TRAIN_WG_GROUP", "1")
-        if wg_group in ("1", "4"):  # "4": the RDB final conv stays on its own ci-split launch (A/B)
-            B = _group_side_wgrads(B, lib, skip_final=wg_group == "4")
-        self.bwd_launches = B
-        self.head_wg = d9h
-        # workspace for the split-K partial sums
-        nbytes = 0
-        for e in B:
-            if e[0] == "wg3":
-                nbytes = max(nbytes, lib.isr_wgrad3x3_workspace_bytes(ctypes.byref(e[1])))
-            elif e[0] == "wg3g":
-                nbytes = max(nbytes, lib.isr_wgrad3x3_group_workspace_bytes(e[1], len(e[2])))
-            elif e[0] == "wg9":
-                nbytes = max(nbytes, lib.isr_wgrad9x9_workspace_bytes(ctypes.byref(e[1])))
-        if nbytes == 0:
-            raise RuntimeError("train plan: could not size the wgrad workspace: "
-                               + lib.isr_last_error().decode(errors="replace"))
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        # the side stream's weight gradients get a workspace of their own (they run concurrently
-        # with the main stream's)
-        self.ws_side = torch.empty(nbytes, dtype=torch.uint8, device=dev) if self.gather else None
-        self.side = (torch.cuda.Stream(dev) if self.gather and _os.environ.get("ISR_TRAIN_SIDE", "1") == "1"
-                     else None)
-        # A/B option (ISR_TRAIN_RED_STREAM=1, off): the side stream's split-K reductions on a third
-        # stream over a ring of RED_RING workspaces (a slot is reused once the reduce that read it
-        # has finished), so the side stream chains only the weight-gradient kernels.  Skipping the
-        # reductions altogether saves 3.3 ms per cfg3 step (tuning probe; script removed, see git history at f92e488),
-        # but moving them off the chain loses 1.2 ms (51.7 / 51.8 vs 50.5 / 50.6 ms, alternating
-        # processes, profiles/r04_train_red_stream_ab.jsonl): their cost is the partials' traffic,
-        # not their place in the chain
-        self.red = None
-        if self.side is not None and _os.environ.get("ISR_TRAIN_RED_STREAM", "0") == "1":
-            self.red = torch.cuda.Stream(dev)
-            self.ws_ring = [self.ws_side] + [torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                                             for _ in range(RED_RING - 1)]
-            self.ev_part = [torch.cuda.Event() for _ in range(RED_RING)]
-            self.ev_red = [torch.cuda.Event() for _ in range(RED_RING)]
-        self.events = {}
-        # gradient offsets per conv: (w, b or None, bn weight or None, bn bias or None)
-        self._conv_goff = []
-        pi = 0
-        for c in self.convs:
-            wo = self._goff[pi]
-            pi += 1
-            bo = None
-            if c.b is not None:
-                bo = self._goff[pi]
-                pi += 1
-            go = bo2 = None
-            if c.bn is not None:
-                go, bo2 = self._goff[pi], self._goff[pi + 1]
-                pi += 2
-            self._conv_goff.append((wo, bo, go, bo2))
-        # data-parallel gradient buckets: the flat buffer in backward order is
-        # [conv1 .. tail] (end of the buffer), RRDB nb-1, ..., RRDB 0, head (start) — contiguous
-        # descending ranges, each complete at its ("ready", id) entry of the backward list
-        first = lambda conv_index: self._conv_goff[conv_index][0]
-        nr = len(self.rdbs)
-        seg = {"tail": (first(1 + 5 * nr), self._gsize), "head": (0, first(1) if nr else self._gsize)}
-        for i in range(nr // 3):
-            seg[i] = (first(1 + 15 * i), first(1 + 15 * (i + 1)))
-        self._segments = seg
+        return B, U
 
-    def _backward_chain(self, B: list) -> list:
+    def _backward_trunk_end(self, g_trunk: ActBuffer) -> list[Step]:
+        """g_f0 = chain + g_T, then LeakyReLU'(f0) of conv0; the head's weight gradient."""
+        ew = ops.ew_combine_desc(self.gf0, g_trunk, 64, sa=1.0, b=self.gT, sb=1.0, m=self.f0, mslope=self.slope0)
+        self.head_wg = ops.wgrad9x9_desc(self.dummy_x, self.gf0, _meta_dw(64, 3, 9, self.device), None, head=True)
+        return [Step("ew", ew), Step("wg9", self.head_wg, conv=self._conv_index[id(self.head)]),
+                Step("ready", id="head")]
+
+    def _backward_chain(self, B: list[Step]) -> list[Step]:
         """The RDB gather convs of the backward (240 for 16 RRDBs) as ONE persistent isr_conv_chain
         launch (trunk.hip: the forward dense block's dependency shape — gather t reads
         E[0:64 + 32 (3 - t)) and writes the next 32 channels, masked by LeakyReLU' of the forward
@@ -445,14 +465,14 @@ class GeneratorTrainPlan:
         52.23 ms per cfg3 step, same box (profiles/r04_train_bwd_chain_ab.jsonl) — the weight
         gradients it pushes behind the chain had been overlapping the per-conv gathers."""
         from .engine import CHAIN_ACQUIRE, ConvChain
-        gathers = [k for k, e in enumerate(B) if e[0] == "conv" and len(e) > 2 and e[2] == "gather"]
+        gathers = [k for k, s in enumerate(B) if s.gather]
         if not gathers:
             return B
         zb = torch.zeros(64, device=self.device)
         self._bchain_bias = zb
         descs = []
         for k in gathers:
-            d = IsrConvDescCopy(B[k][1])
+            d = _copy_conv_desc(B[k].desc)
             d.bias = zb.data_ptr()
             if d.cout == 64:
                 d.r1_cn = 0  # fold the RDB output gradient (r1 aliases the gather input)
@@ -463,15 +483,36 @@ class GeneratorTrainPlan:
         except ValueError as err:
             import warnings
             warnings.warn(f"training backward gathers run per conv (persistent chain refused: {err})")
-            self.bchain = None
             return B
         first, last = gathers[0], gathers[-1]
-        body = [e for e in B[first:last + 1] if not (e[0] == "conv" and len(e) > 2 and e[2] == "gather")
-                and e[0] not in ("evrec", "evwait")]
-        head = [e for e in B[:first] if not (e[0] == "ready" and e[1] == "tail")]
-        tail_ready = [e for e in B[:first] if e[0] == "ready" and e[1] == "tail"]
-        return (head + [("bchain", self.bchain)] + tail_ready + [("evrec", "bchain"), ("evwait", "bchain")]
+
+        def tail_ready(s: Step) -> bool:
+            return s.kind == "ready" and s.id == "tail"
+
+        body = [s for s in B[first:last + 1] if not s.gather and s.kind not in ("evrec", "evwait")]
+        return ([s for s in B[:first] if not tail_ready(s)] + [Step("bchain", self.bchain.desc)]
+                + [s for s in B[:first] if tail_ready(s)] + [Step("evrec", id="bchain"), Step("evwait", id="bchain")]
                 + body + B[last + 1:])
+
+    def _size_workspaces(self, opt: _Options) -> None:
+        """The split-K partial sums' workspace (one size fits every weight gradient of the
+        program) and the side stream with a workspace of its own: its weight gradients run
+        concurrently with the main stream's."""
+        lib, nbytes = self.lib, 0
+        for s in self.bwd_launches:
+            if s.kind == "wg3":
+                nbytes = max(nbytes, lib.isr_wgrad3x3_workspace_bytes(ctypes.byref(s.desc)))
+            elif s.kind == "wg3g":
+                nbytes = max(nbytes, lib.isr_wgrad3x3_group_workspace_bytes(s.desc, len(s.conv)))
+            elif s.kind == "wg9":
+                nbytes = max(nbytes, lib.isr_wgrad9x9_workspace_bytes(ctypes.byref(s.desc)))
+        if nbytes == 0:
+            raise RuntimeError("train plan: could not size the wgrad workspace: "
+                               + lib.isr_last_error().decode(errors="replace"))
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.side = torch.cuda.Stream(self.device) if opt.side else None
+        self.ws_side = torch.empty_like(self.ws) if opt.side else None
+        self.events = {}
 
     # -------------------------------------------------------------- execution
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -485,21 +526,17 @@ class GeneratorTrainPlan:
         self.tail_desc.y = y.data_ptr()
         self.head_wg.p = x.data_ptr()
         st = ops._stream()
-        byref = ctypes.byref
         lib = self.lib
-        for e in self.fwd_launches:
-            if e[0] == "bnf":
-                d, bst = e[1], e[2]
-                bst.acc.zero_()
-                for fn in (lib.isr_bn_stats, lib.isr_bn_finalize, lib.isr_bn_apply):
-                    rc = fn(byref(d), st)
-                    if rc != 0:
-                        ops.check(rc, "train forward (bn)")
+        launch = {"head": lib.isr_head9x9_fwd, "conv": lib.isr_conv3x3_fwd, "tail": lib.isr_tail9x9_fwd,
+                  "chain": self.chain.fn if self.chain is not None else None}
+        for s in self.fwd_launches:
+            if s.kind == "bnf":
+                ops.bn_forward(s.desc, s.bn_state)
                 continue
-            rc = e[0](byref(e[1]), st)
+            rc = launch[s.kind](ctypes.byref(s.desc), st)
             if rc != 0:
                 ops.check(rc, "train forward")
-            if self.chain is not None and e[1] is self.chain.desc:
+            if s.kind == "chain":
                 self.trunk_done = torch.cuda.Event()
                 self.trunk_done.record()
         if self.chain is not None:
@@ -514,80 +551,57 @@ class GeneratorTrainPlan:
         torch.mul(gy, 1.0 - self.y * self.y, out=self.gp)  # tanh' (utils/models.py:607 act=Tanh)
         grads = torch.empty(self._gsize, device=self.device)
         gbase = grads.data_ptr()
-        lib, st, byref = self.lib, ops._stream(), ctypes.byref
-        ws, wsn = self.ws.data_ptr(), self.ws.numel()
-        main = torch.cuda.current_stream(self.device)
+        lib, byref = self.lib, ctypes.byref
+        main, side = torch.cuda.current_stream(self.device), self.side
+        on_main = (self.ws.data_ptr(), self.ws.numel(), ops._stream())
         side_used = False
-        if self.side is not None:
-            self.side.wait_stream(main)  # `grads` and the forward's activations are ready
-            sst = ctypes.c_void_p(self.side.cuda_stream)
+        if side is not None:
+            side.wait_stream(main)  # `grads` and the forward's activations are ready
+            on_side = (self.ws_side.data_ptr(), self.ws_side.numel(), ctypes.c_void_p(side.cuda_stream))
+        st = on_main[2]
         group = self.gen.__dict__.get("_isr_grad_group")
         ddp = _Buckets(self, grads, group, main) if group is not None else None
-        red = self.red
-        if red is not None:
-            rst = ctypes.c_void_p(red.cuda_stream)
-            red_used = [False] * RED_RING
-            nside = 0
-        side_done = red if red is not None else self.side  # where a side-produced segment completes
-        for e in self.bwd_launches:
-            kind, d = e[0], e[1]
+
+        def patch(d, conv):  # this call's dw / db into a weight-gradient descriptor
+            wo, bo = self._conv_goff[conv][:2]
+            d.dw = gbase + 4 * wo
+            d.db = gbase + 4 * bo if bo is not None else None
+
+        for s in self.bwd_launches:
+            kind, d = s.kind, s.desc
             if kind == "ready":
                 if ddp is not None:
-                    ddp.ready(d, side_done if (e[2] and self.side is not None) else main)
+                    ddp.ready(s.id, side if (s.side and side is not None) else main)
                 continue
-            if kind in ("evrec", "evwait") and self.side is None:
+            if kind in ("evrec", "evwait"):
+                if side is None:
+                    continue
+                if kind == "evrec":
+                    ev = self.events.get(s.id)
+                    if ev is None:
+                        ev = self.events[s.id] = torch.cuda.Event()
+                    ev.record(main)
+                else:
+                    side.wait_event(self.events[s.id])
+                    side_used = True
                 continue
-            if kind == "evrec":
-                ev = self.events.get(d)
-                if ev is None:
-                    ev = self.events[d] = torch.cuda.Event()
-                ev.record(main)
-                continue
-            if kind == "evwait":
-                self.side.wait_event(self.events[d])
-                side_used = True
-                continue
+            where = on_side if (s.side and side is not None) else on_main
             if kind == "conv":
                 rc = lib.isr_conv3x3_fwd(byref(d), st)
             elif kind == "bchain":
-                rc = d.fn(byref(d.desc), st)
+                rc = self.bchain.fn(byref(d), st)
             elif kind == "bnb":
-                _, _, go, bo2 = self._conv_goff[e[2]]
+                _, _, go, bo2 = self._conv_goff[s.conv]
                 d.dgamma, d.dbeta = gbase + 4 * go, gbase + 4 * bo2
-                e[3].acc.zero_()
-                rc = lib.isr_bn_bwd_reduce(byref(d), st)
-                if rc == 0:
-                    rc = lib.isr_bn_bwd_apply(byref(d), st)
+                ops.bn_backward(d, s.bn_state)
+                continue
             elif kind == "wg3" or kind == "wg9":
-                wo, bo = self._conv_goff[e[2]][:2]
-                d.dw = gbase + 4 * wo
-                d.db = gbase + 4 * bo if bo is not None else None
-                if kind == "wg3" and e[3] and red is not None:
-                    k = nside % RED_RING
-                    nside += 1
-                    wsk = self.ws_ring[k]
-                    if red_used[k]:
-                        self.side.wait_event(self.ev_red[k])  # the slot's previous reduce has read it
-                    rc = lib.isr_wgrad3x3_partials(byref(d), wsk.data_ptr(), wsk.numel(), sst)
-                    if rc == 0:
-                        self.ev_part[k].record(self.side)
-                        red.wait_event(self.ev_part[k])
-                        rc = lib.isr_wgrad3x3_reduce(byref(d), wsk.data_ptr(), wsk.numel(), rst)
-                        self.ev_red[k].record(red)
-                        red_used[k] = True
-                elif kind == "wg3" and e[3] and self.side is not None:
-                    rc = lib.isr_wgrad3x3(byref(d), self.ws_side.data_ptr(), self.ws_side.numel(), sst)
-                else:
-                    rc = (lib.isr_wgrad3x3 if kind == "wg3" else lib.isr_wgrad9x9)(byref(d), ws, wsn, st)
+                patch(d, s.conv)
+                rc = (lib.isr_wgrad3x3 if kind == "wg3" else lib.isr_wgrad9x9)(byref(d), *where)
             elif kind == "wg3g":  # one RDB's weight gradients in one launch (isr_wgrad3x3_group)
-                for k, c in enumerate(e[2]):
-                    wo, bo = self._conv_goff[c][:2]
-                    d[k].dw = gbase + 4 * wo
-                    d[k].db = gbase + 4 * bo if bo is not None else None
-                if self.side is not None:
-                    rc = lib.isr_wgrad3x3_group(d, len(e[2]), self.ws_side.data_ptr(), self.ws_side.numel(), sst)
-                else:
-                    rc = lib.isr_wgrad3x3_group(d, len(e[2]), ws, wsn, st)
+                for k, c in enumerate(s.conv):
+                    patch(d[k], c)
+                rc = lib.isr_wgrad3x3_group(d, len(s.conv), *where)
             elif kind == "head":
                 rc = lib.isr_head9x9_fwd(byref(d), st)
             else:
@@ -595,9 +609,7 @@ class GeneratorTrainPlan:
             if rc != 0:
                 ops.check(rc, f"train backward ({kind})")
         if side_used:
-            main.wait_stream(self.side)
-            if red is not None:
-                main.wait_stream(red)
+            main.wait_stream(side)
         if ddp is not None:
             ddp.finish()  # the main stream waits for every bucket, then the mean
         out = []
@@ -606,46 +618,35 @@ class GeneratorTrainPlan:
         return out
 
 
-def IsrConvDescCopy(d):
+def _copy_conv_desc(d):
     """An independent copy of an isr_conv_desc (ctypes structures assign by value)."""
     c = type(d)()
     ctypes.pointer(c)[0] = d
     return c
 
 
-# workspaces in the ring of the side stream's split-K partials (train plan with a reduce stream)
-RED_RING = 4
-
-
-def _group_side_wgrads(B: list, lib, skip_final: bool = False) -> list:
+def _group_side_wgrads(B: list[Step], lib) -> list[Step]:
     """Runs of consecutive side-stream 3x3 weight gradients (one RDB's five convs: one dense
-    buffer, one gradient buffer) become ONE ("wg3g", descriptor array, conv indices, True) entry
+    buffer, one gradient buffer) become ONE "wg3g" step (descriptor array, conv indices)
     launched through isr_wgrad3x3_group — one grid over all their (co, ci) tile pairs, ~5x fewer
     split-K partials.  A run the library refuses to group stays as separate launches."""
     out, run = [], []
 
     def flush():
         if len(run) >= 2:
-            arr = (_lib.IsrWgradDesc * len(run))(*[r[1] for r in run])
+            arr = (_lib.IsrWgradDesc * len(run))(*[s.desc for s in run])
             if lib.isr_wgrad3x3_group_workspace_bytes(arr, len(run)) > 0:
-                out.append(("wg3g", arr, [r[2] for r in run], True))
+                out.append(Step("wg3g", arr, conv=[s.conv for s in run], side=True))
                 run.clear()
                 return
         out.extend(run)
         run.clear()
 
-    def groupable(e):
-        return e[0] == "wg3" and e[3] and not (skip_final and e[1].cout == 64 and e[1].cin == 192)
-
-    for e in B:
-        if groupable(e) and len(run) < 5:
-            run.append(e)
-            continue
-        flush()
-        if groupable(e):
-            run.append(e)
-        else:
-            out.append(e)
+    for s in B:
+        groupable = s.kind == "wg3" and s.side
+        if not (groupable and len(run) < 5):
+            flush()
+        (run if groupable else out).append(s)
     flush()
     return out
 

@@ -31,9 +31,9 @@ def _oracle_grads(sd, x, hr, blocks, scale, loss_fn):
     return loss.item(), {k: v.grad for k, v in sdc.items() if v.grad is not None}
 
 
-@pytest.mark.parametrize("blocks,scale,n,h,w,loss", [(1, 4, 2, 20, 24, "mse"), (2, 2, 2, 36, 40, "l1"),
-                                                     (1, 4, 1, 33, 17, "mse")])
-def test_eresnet_train_step_grads(blocks, scale, n, h, w, loss):
+def _eresnet_step_vs_oracle(blocks, scale, n, h, w, loss):
+    """One EResNet training step against autograd of the fp32 oracle at the module's bars;
+    returns the step's training plan."""
     torch.manual_seed(0)
     m = models.EResNet(blocks, 0.2, scale)
     m.load_state_dict(synth_state_dict(m.state_dict(), 7))
@@ -48,9 +48,10 @@ def test_eresnet_train_step_grads(blocks, scale, n, h, w, loss):
     l = loss_fn(y, hr.to(DEV))
     l.backward()
     torch.cuda.synchronize()
+    plan = m.__dict__["_isr_train_plan"]
     # the training forward's trunk runs on the persistent trunk kernel (a refused layer table
     # falls back to per-conv launches: correct but ~3.5 ms slower per SRGAN step)
-    assert m.__dict__["_isr_train_plan"].chain is not None
+    assert plan.chain is not None
     assert abs(l.item() - ref_loss) <= 1e-3 * abs(ref_loss) + 1e-5, (l.item(), ref_loss)
     worst = []
     for name, p in m.named_parameters():
@@ -63,6 +64,21 @@ def test_eresnet_train_step_grads(blocks, scale, n, h, w, loss):
         assert rel <= 5e-2 and cos >= 0.998, f"{name}: rel {rel:.3e} cos {cos:.5f}"
     worst.sort(reverse=True)
     print("worst grads:", worst[:3])
+    return plan
+
+
+@pytest.mark.parametrize("blocks,scale,n,h,w,loss", [(1, 4, 2, 20, 24, "mse"), (2, 2, 2, 36, 40, "l1"),
+                                                     (1, 4, 1, 33, 17, "mse")])
+def test_eresnet_train_step_grads(blocks, scale, n, h, w, loss):
+    _eresnet_step_vs_oracle(blocks, scale, n, h, w, loss)
+
+
+def test_eresnet_rotating_walk_without_bn(monkeypatch):
+    """ISR_TRAIN_GATHER=0: the rotating backward walk on a model without BatchNorm (its
+    `bn is None` branches, which a partly BN-fused ResNet reaches too), at the same bars."""
+    monkeypatch.setenv("ISR_TRAIN_GATHER", "0")
+    plan = _eresnet_step_vs_oracle(1, 4, 2, 20, 24, "mse")
+    assert plan.gather is False and plan.chain is not None
 
 
 def test_train_step_updates_and_repacks():
@@ -144,14 +160,20 @@ def test_resnet_train_step_all_grads_vs_oracle():
             torch.testing.assert_close(b.cpu(), sd[name], rtol=1e-2, atol=1e-3)
 
 
-@pytest.mark.parametrize("env,bitwise", [({"ISR_TRAIN_RED_STREAM": "1"}, True), ({"ISR_TRAIN_WG_GROUP": "0"}, False),
+@pytest.mark.parametrize("env,bitwise", [({"ISR_TRAIN_SIDE": "0"}, True), ({"ISR_TRAIN_WG_GROUP": "0"}, False),
                                          ({"ISR_TRAIN_BWD_CHAIN": "1"}, False)])
 def test_backward_options_same_gradients(monkeypatch, env, bitwise):
-    """The A/B options of the backward plan give the production gradients: the side stream's
-    reductions on a third stream (same partials, same sums: bit for bit), the RDB weight
-    gradients as separate launches instead of one grouped launch (other split-K partition), and
-    the RDB gather convs on the persistent backward chain instead of per-conv launches (the chain
-    folds the RDB output gradient by MFMA, the per-conv launch adds it in the epilogue)."""
+    """The options of the backward plan give the production gradients: the weight gradients on
+    the main stream instead of the side stream (the same descriptors through the same kernels
+    with a workspace of the same size, and split-K sums of a fixed order: bit for bit), the RDB
+    weight gradients as separate launches instead of one grouped launch (other split-K
+    partition), and the RDB gather convs on the persistent backward chain instead of per-conv
+    launches (the chain folds the RDB output gradient by MFMA, the per-conv launch adds it in the
+    epilogue).  The reduce-stream case left with its option (the side stream's reductions on a
+    third stream, measured slower and removed); that partials + reduce equal one call bit
+    for bit stays pinned on the library, in test_gpu_kernels.py::
+    test_wgrad3x3_partials_then_reduce_equals_one_call and the partials / reduce case of
+    test_gpu_exact.py."""
     torch.manual_seed(0)
     sd = synth_state_dict(models.EResNet(2, 0.2, 2).state_dict(), 13)
     lr, hr01 = synth_lr_batch(2, 32, 32, seed=17, scale=2)
@@ -163,18 +185,16 @@ def test_backward_options_same_gradients(monkeypatch, env, bitwise):
         m = m.to(DEV).train()
         F.l1_loss(m(x), hr).backward()
         torch.cuda.synchronize()
-        return {k: p.grad.clone() for k, p in m.named_parameters()}
+        return {k: p.grad.clone() for k, p in m.named_parameters()}, m.__dict__["_isr_train_plan"]
 
-    ref = grads()
+    ref, _ = grads()
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    got = grads()
+    got, plan = grads()
     if "ISR_TRAIN_BWD_CHAIN" in env:
-        m = models.EResNet(2, 0.2, 2)
-        m.load_state_dict(sd)
-        m = m.to(DEV).train()
-        F.l1_loss(m(x), hr).backward()
-        assert m.__dict__["_isr_train_plan"].bchain is not None  # the option really ran the chain
+        assert plan.bchain is not None  # the option really ran the chain
+    if "ISR_TRAIN_SIDE" in env:
+        assert plan.side is None
     for k in ref:
         if bitwise:
             assert torch.equal(got[k], ref[k]), k
