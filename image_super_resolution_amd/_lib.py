@@ -148,6 +148,21 @@ class IsrYuv16Desc(ctypes.Structure):
                 ("src", c_void_p), ("dst", c_void_p)]
 
 
+class IsrDihedralDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("c", c_int32), ("h", c_int32), ("w", c_int32), ("elem", c_int32), ("op", c_int32),
+                ("ops", c_void_p), ("x", c_void_p), ("y", c_void_p)]
+
+
+class IsrEnsembleExpandDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("x", c_void_p), ("even", c_void_p),
+                ("odd", c_void_p)]
+
+
+class IsrEnsembleReduceDesc(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("even", c_void_p), ("odd", c_void_p),
+                ("y", c_void_p), ("y_u8", c_int32)]
+
+
 HLS_PARTIAL_BLOCKS = 32  # ISR_HLS_PARTIAL_BLOCKS
 MT_TENSOR_BYTES = 40 # isr_mt_tensor: 4 pointers + int64
 MT_CHUNK_BYTES = 16   # isr_mt_chunk: int32 t, int32 len, int64 start
@@ -234,6 +249,10 @@ SIGNATURES = {
     "isr_yuv_coeffs_depth": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "isr_yuv420_to_rgb_16": (c_int32, [POINTER(IsrYuv16Desc), c_void_p]),
     "isr_rgb_to_yuv420_16": (c_int32, [POINTER(IsrYuv16Desc), c_void_p]),
+    "isr_dihedral": (c_int32, [POINTER(IsrDihedralDesc), c_void_p]),
+    "isr_dihedral_inverse": (c_int32, [c_int32]),
+    "isr_ensemble_expand_u8": (c_int32, [POINTER(IsrEnsembleExpandDesc), c_void_p]),
+    "isr_ensemble_reduce": (c_int32, [POINTER(IsrEnsembleReduceDesc), c_void_p]),
     "isr_last_error": (ctypes.c_char_p, []),
     "isr_version": (c_int32, []),
 }

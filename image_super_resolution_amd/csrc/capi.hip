@@ -66,6 +66,10 @@ int resample_u8_dispatch(const isr_resample_desc* d, hipStream_t s);
 int blur_u8_dispatch(const isr_blur_desc* d, hipStream_t s);
 int yuv_dispatch(const isr_yuv_desc* d, int to_rgb, hipStream_t s);
 int yuv16_dispatch(const isr_yuv16_desc* d, int to_rgb, hipStream_t s);
+int dihedral_dispatch(const isr_dihedral_desc* d, hipStream_t s);
+int ensemble_expand_u8_dispatch(const isr_ensemble_expand_desc* d, hipStream_t s);
+int ensemble_reduce_dispatch(const isr_ensemble_reduce_desc* d, hipStream_t s);
+int dihedral_inverse(int op);
 }  // namespace isr
 
 static thread_local char g_err[512] = "";
@@ -962,6 +966,63 @@ int isr_yuv420_to_rgb_16(const isr_yuv16_desc* d, isr_stream_t s) {
 int isr_rgb_to_yuv420_16(const isr_yuv16_desc* d, isr_stream_t s) {
     if (int rc = yuv16_ok("rgb_to_yuv420_16", d, 0)) return rc;
     return launched(isr::yuv16_dispatch(d, 0, (hipStream_t)s), "rgb_to_yuv420_16");
+}
+
+// ---- dihedral transforms ----
+// The shape rule of the three entry points: n in [1, max_n], c in [1, 65535], h, w >= 1, one plane below 2^31
+// elements (a tile's coordinates are ints).
+static int dihedral_shape_ok(const char* what, int n, int max_n, int c, int h, int w) {
+    if (n < 1 || n > max_n) return fail(ISR_ERR_BAD_DESC, "%s: bad batch n=%d (n in [1, %d])", what, n, max_n);
+    if (c < 1 || c > 65535) return fail(ISR_ERR_BAD_DESC, "%s: bad channel count c=%d (c in [1, 65535])", what, c);
+    if (h < 1 || w < 1) return fail(ISR_ERR_BAD_DESC, "%s: image %dx%d smaller than 1 x 1", what, h, w);
+    if ((long long)h * w >= (1ll << 31))
+        return fail(ISR_ERR_UNSUPPORTED, "%s: a plane of h*w = %lld does not fit 31 bits (%dx%d)", what, (long long)h * w,
+                    h, w);
+    return ISR_OK;
+}
+
+static int dihedral_launched(int rc, const char* what) {
+    if (rc == -2) return fail(ISR_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups", what);
+    return launched(rc, what);
+}
+
+int isr_dihedral_inverse(int op) {
+    if (op < 0 || op > 7) return fail(ISR_ERR_BAD_DESC, "dihedral_inverse: op %d is not in 0..7", op);
+    return isr::dihedral_inverse(op);
+}
+
+int isr_dihedral(const isr_dihedral_desc* d, isr_stream_t s) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "dihedral: null descriptor");
+    if (!d->x || !d->y) return fail(ISR_ERR_BAD_DESC, "dihedral: null x / y");
+    if (d->x == d->y) return fail(ISR_ERR_BAD_DESC, "dihedral: y must not be x");
+    if (d->elem != 1 && d->elem != 4) return fail(ISR_ERR_UNSUPPORTED, "dihedral: elem %d is not 1 or 4 bytes", d->elem);
+    if (!aligned(d->elem, {d->x, d->y}) || !aligned(4, {d->ops}))
+        return fail(ISR_ERR_BAD_DESC, "dihedral: x and y must be aligned to elem = %d bytes, ops 4-byte aligned", d->elem);
+    if (int rc = dihedral_shape_ok("dihedral", d->n, 65535, d->c, d->h, d->w)) return rc;
+    if (d->ops && d->h != d->w)
+        return fail(ISR_ERR_UNSUPPORTED, "dihedral: per-image ops need square images (h == w), not %dx%d", d->h, d->w);
+    if (!d->ops && (d->op < 0 || d->op > 7)) return fail(ISR_ERR_UNSUPPORTED, "dihedral: op %d is not in 0..7", d->op);
+    return dihedral_launched(isr::dihedral_dispatch(d, (hipStream_t)s), "dihedral");
+}
+
+int isr_ensemble_expand_u8(const isr_ensemble_expand_desc* d, isr_stream_t s) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "ensemble_expand_u8: null descriptor");
+    if (!d->x || !d->even || !d->odd) return fail(ISR_ERR_BAD_DESC, "ensemble_expand_u8: null x / even / odd");
+    if (d->x == d->even || d->x == d->odd || d->even == d->odd)
+        return fail(ISR_ERR_BAD_DESC, "ensemble_expand_u8: x, even and odd must not be the same buffer");
+    if (int rc = dihedral_shape_ok("ensemble_expand_u8", d->n, 16383, 3, d->h, d->w)) return rc;
+    return dihedral_launched(isr::ensemble_expand_u8_dispatch(d, (hipStream_t)s), "ensemble_expand_u8");
+}
+
+int isr_ensemble_reduce(const isr_ensemble_reduce_desc* d, isr_stream_t s) {
+    if (!d) return fail(ISR_ERR_BAD_DESC, "ensemble_reduce: null descriptor");
+    if (!d->even || !d->odd || !d->y) return fail(ISR_ERR_BAD_DESC, "ensemble_reduce: null even / odd / y");
+    if (d->y == (const void*)d->even || d->y == (const void*)d->odd || d->even == d->odd)
+        return fail(ISR_ERR_BAD_DESC, "ensemble_reduce: even, odd and y must not be the same buffer");
+    if (!aligned(4, {d->even, d->odd}) || !aligned(d->y_u8 ? 1 : 4, {d->y}))
+        return fail(ISR_ERR_BAD_DESC, "ensemble_reduce: even, odd and an fp32 y must be 4-byte aligned");
+    if (int rc = dihedral_shape_ok("ensemble_reduce", d->n, 16383, 3, d->h, d->w)) return rc;
+    return dihedral_launched(isr::ensemble_reduce_dispatch(d, (hipStream_t)s), "ensemble_reduce");
 }
 
 }  // extern "C"

@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch.utils.data import Dataset
 
-from . import _lib, degrade, ops
+from . import _lib, degrade, dihedral, ops
 
 IMG_FORMATS = (".bmp", ".jpg", ".jpeg", ".png", ".tif", ".tiff", ".webp")
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -69,6 +69,47 @@ class SRCropDataset(Dataset):
         return torch.from_numpy(np.ascontiguousarray(a[y:y + t, x:x + t])).permute(2, 0, 1).contiguous()
 
 
+AUGMENTS = ("none", "flip", "dihedral")
+AUGMENT_SEED_OFFSET = 0x0D4  # the augmentation generator's seed is the transform's `seed` plus this
+
+
+class _Augment:
+    """The geometric training augmentation GPUTransform and NoisyTransform share: per image one op of the
+    dihedral group (dihedral.py), applied to the clean uint8 crops in ONE isr_dihedral launch before anything
+    else.  "flip" draws k in {0, 4} (a mirror along the width or nothing), "dihedral" k uniform in 0..7
+    (square crops only); each by exactly one torch.randint(0, 2 or 8, (n,), generator=self.gen, device=...)
+    per call (x 4 for flip), never read back.  self.gen is a device generator of its own, seeded with
+    seed + AUGMENT_SEED_OFFSET, so no other draw of the transform moves.  "none" draws and launches nothing."""
+
+    def __init__(self, who: str, augment: str, seed: int, device):
+        if augment not in AUGMENTS:
+            raise ValueError(f"{who}: augment {augment!r} is not one of {', '.join(AUGMENTS)}")
+        self.who, self.mode, self.device, self.gen = who, augment, device, None
+        if augment != "none" and torch.device(device).type == "cuda":
+            self.gen = torch.Generator(device=device).manual_seed(seed + AUGMENT_SEED_OFFSET)
+
+    def __call__(self, crops_u8: torch.Tensor) -> torch.Tensor:
+        if self.mode == "none":
+            return crops_u8
+        if self.gen is None:
+            raise RuntimeError(f"{self.who}: augment={self.mode!r} is a HIP kernel (MI355X only); device "
+                               f"{self.device!r} has no such path (there is no host fallback)")
+        x = degrade._checked(crops_u8, self.who, on_device=False).to(self.device, non_blocking=True)
+        if self.mode == "dihedral" and x.shape[-2] != x.shape[-1]:
+            raise ValueError(f"{self.who}: augment='dihedral' turns crops by 90 degrees and needs square ones, got "
+                             f"{x.shape[-2]}x{x.shape[-1]} (augment='flip' takes any shape)")
+        n = x.shape[0]
+        if self.mode == "flip":
+            ids = torch.randint(0, 2, (n,), generator=self.gen, device=x.device).to(torch.int32) * 4
+            if x.shape[-2] != x.shape[-1]:
+                # a mirror along the width keeps the shape, but per-image ops are for square batches: flip
+                # every image into a second batch (one launch) and let the ids choose
+                return torch.where((ids != 0).view(n, 1, 1, 1), dihedral.apply(x, 4), x)
+        else:
+            ids = torch.randint(0, 8, (n,), generator=self.gen, device=x.device).to(torch.int32)
+        return dihedral.apply(x, ids)
+
+
 class GPUTransform:
     """Batched (hr, lr) from uint8 HR crops on the device:
     lr = Normalize(Resize(crop, T/scale)) (albumentations Resize = cv2 INTER_LINEAR,
@@ -95,13 +136,20 @@ class GPUTransform:
     lr is the same resize + Normalize of the degraded copy (one more launch of the transform's
     kernel).  The `random` draw above happens before the degradation's draws and from a generator
     of its own, so it is the same with and without `degrade`; with every probability 0 lr is
-    unchanged too.  HIP only."""
+    unchanged too.  HIP only.
+
+    `augment` ("none", "flip" or "dihedral": _Augment) transforms the clean crops first, ahead of `degrade` and
+    of both resizes, so hr and lr show the same transformed picture; its ids come from a generator of its
+    own (seed + AUGMENT_SEED_OFFSET), so the `random` filter draw and the degradation's draws are the same
+    with and without it.  "none" (the default) launches nothing and changes no output bit.  HIP only."""
 
     LR_FILTERS = ("cv2", "nearest", "box", "bilinear", "hamming", "bicubic", "lanczos", "random")
     RANDOM_FILTERS = ("bicubic", "bilinear", "box", "nearest")
 
     def __init__(self, scale: int, hr_norm: bool = False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda",
-                 lr_filter: str = "cv2", seed: int = 0, degrade: "LRDegrade | None" = None):
+                 lr_filter: str = "cv2", seed: int = 0, degrade: "LRDegrade | None" = None,
+                 augment: str = "none"):
+        self.augment = _Augment("GPUTransform", augment, seed, device)
         if lr_filter not in self.LR_FILTERS:
             raise ValueError(f"GPUTransform: lr_filter {lr_filter!r} is not one of {', '.join(self.LR_FILTERS)}")
         self.scale, self.hr_norm = scale, hr_norm
@@ -120,9 +168,9 @@ class GPUTransform:
         if self.lr_filter != "cv2" and not on_gpu:
             raise RuntimeError(f"GPUTransform: lr_filter={self.lr_filter!r} is a HIP kernel (MI355X only); device "
                                f"{self.device!r} has no such path (there is no host fallback)")
-        if self.lr_filter == "cv2" and not on_gpu and self.degrade is None:
+        if self.lr_filter == "cv2" and not on_gpu and self.degrade is None and self.augment.mode == "none":
             return self._cv2_on_cpu(crops_u8)
-        x = self._crops(crops_u8)
+        x = self.augment(self._crops(crops_u8))
         backend = self._cv2 if self.lr_filter == "cv2" else self._pillow(x)
         if self.degrade is None:
             return backend(x, True, True)
@@ -236,11 +284,17 @@ class NoisyTransform:
     stages exchange uint8 images as the reference's do (GaussNoise's result is truncated to
     uint8), the extra draws follow the three GaussNoise draws, and the stages are HIP kernels:
     a CPU device raises.  `NoisyTransform.reference(...)` is the reference's pipeline
-    (iso_p = jpeg_p = 0.5)."""
+    (iso_p = jpeg_p = 0.5).
+
+    `augment` ("none", "flip" or "dihedral": _Augment) transforms the uint8 crops before all of the above,
+    so clean and noisy show the same transformed picture; its ids come from a generator of its own
+    (seed + AUGMENT_SEED_OFFSET), so the noise draws are the same with and without it.  "none" (the
+    default) launches nothing.  HIP only."""
 
     def __init__(self, mean=IMAGENET_MEAN, std=IMAGENET_STD, var_limit=(10.0, 50.0), p: float = 0.5,
                  device="cuda", seed: int = 0, iso_p: float = 0.0, jpeg_p: float = 0.0, jpeg_quality=(50, 75),
-                 iso_color_shift=(0.01, 0.05), iso_intensity=(0.1, 0.5)):
+                 iso_color_shift=(0.01, 0.05), iso_intensity=(0.1, 0.5), augment: str = "none"):
+        self.augment = _Augment("NoisyTransform", augment, seed, device)
         self.mean = torch.tensor(mean, device=device).view(1, 3, 1, 1)
         self.std = torch.tensor(std, device=device).view(1, 3, 1, 1)
         self.var_limit, self.p, self.device = var_limit, p, device
@@ -257,7 +311,7 @@ class NoisyTransform:
         return cls(*args, **kw)
 
     def __call__(self, crops_u8: torch.Tensor):
-        x = crops_u8.to(self.device, non_blocking=True).float()
+        x = self.augment(crops_u8).to(self.device, non_blocking=True).float()
         noise = _gauss_noise(x.shape, x.shape[0], self.gen, self.device, self.var_limit, self.p)
         hr = x / 255.0 * 2.0 - 1.0
         if self.iso_p > 0 or self.jpeg_p > 0:

@@ -31,7 +31,7 @@ from typing import Callable, Sequence
 
 import torch
 
-from . import engine
+from . import dihedral, engine
 
 
 @dataclass(frozen=True)
@@ -225,6 +225,18 @@ def forward_bytes(n: int, h: int, w: int, n_scalers: int) -> int:
     return plan_bytes(n, h, w, n_scalers) + n * 3 * h * w * (1 + s2) + 16 * (8 << 20)
 
 
+def ensemble_forward_bytes(n: int, h: int, w: int, n_scalers: int) -> int:
+    """Device bytes one self-ensembled forward of n tiles of h x w needs (TileUpscaler(self_ensemble=True)):
+    the two member batches `even` [4n, 3, h, w] and `odd` [4n, 3, w, h] run one after the other, but both
+    plans (4n images each) stay cached, and both fp32 member outputs are alive when they are reduced: two
+    plans, the uint8 tiles and their 8 copies, two fp32 [4n, 3, s h, s w] outputs, the uint8 result, and
+    the allocator slack of forward_bytes."""
+    s2 = 4 ** n_scalers
+    px = n * 3 * h * w
+    return (plan_bytes(4 * n, h, w, n_scalers) + plan_bytes(4 * n, w, h, n_scalers) + px * 9 + 2 * 4 * px * s2 * 4
+            + px * s2 + 16 * (8 << 20))
+
+
 def device_budget(device, reserve: float = 0.1) -> int | None:
     """Bytes a new forward may allocate on `device`: the device's free memory plus what torch's
     caching allocator holds unused, less `reserve` of the total (None off the GPU)."""
@@ -240,7 +252,9 @@ class GeneratorRunner:
     """uint8 batch runner on the HIP generator: one plan (engine.make_plan) per (b, h, w),
     kept in a least-recently-used cache bounded by `max_plans` and `max_bytes` (plan
     activation buffers; a 4 x 576² cfg4 plan is ~5 GB), so a still with many ragged
-    tile shapes does not hold one full set of buffers per shape."""
+    tile shapes does not hold one full set of buffers per shape.  `run_f32` is the same forward with the
+    fp32 tanh output ([-1, 1], nothing rounded to 8 bits): its plans share the cache under keys of their own,
+    (b, h, w, "f32"), so the uint8 plans are the ones they always were."""
 
     def __init__(self, gw: engine.GeneratorWeights, mean, std, device, max_plans: int = 16,
                  max_bytes: int = 32 << 30):
@@ -251,23 +265,30 @@ class GeneratorRunner:
         self.plans: "OrderedDict[tuple[int, int, int], object]" = OrderedDict()
 
     def cached_bytes(self) -> int:
-        return sum(plan_bytes(n, h, w, len(self.gw.scalers)) for n, h, w in self.plans)
+        return sum(plan_bytes(n, h, w, len(self.gw.scalers)) for n, h, w, *_ in self.plans)
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        return self._run(x, True)
+
+    def run_f32(self, x: torch.Tensor) -> torch.Tensor:
+        """uint8 [b, 3, h, w] -> the generator's fp32 tanh output [b, 3, s h, s w] (a plan with out_u8=False)."""
+        return self._run(x, False)
+
+    def _run(self, x: torch.Tensor, out_u8: bool) -> torch.Tensor:
         if x.dtype != torch.uint8 or not x.is_cuda:
             raise ValueError("GeneratorRunner expects a uint8 CUDA batch")
         n, _, h, w = x.shape
-        key = (n, h, w)
+        key = (n, h, w) if out_u8 else (n, h, w, "f32")
         plan = self.plans.get(key)
         if plan is None:
             need = plan_bytes(n, h, w, len(self.gw.scalers))
             while self.plans and (len(self.plans) >= self.max_plans or self.cached_bytes() + need > self.max_bytes):
                 self.plans.popitem(last=False)  # evict least recently used (its buffers return to torch's pool)
-            plan = engine.make_plan(self.gw, n, h, w, self.device, True, True, self.mean, self.std)
+            plan = engine.make_plan(self.gw, n, h, w, self.device, True, out_u8, self.mean, self.std)
             self.plans[key] = plan
         else:
             self.plans.move_to_end(key)
-        out = torch.empty(plan.out_shape, dtype=torch.uint8, device=self.device)
+        out = torch.empty(plan.out_shape, dtype=torch.uint8 if out_u8 else torch.float32, device=self.device)
         return plan.run(x.contiguous(), out)
 
     def verify(self) -> None:
@@ -307,7 +328,8 @@ class TileUpscaler:
     """
 
     def __init__(self, runner: BatchRunner, scale: int, window: int = 96, halo: int = 0, batch: int = 8,
-                 device="cuda", shard: str = "windows", gather: str = "device", mem_budget: int | None = None):
+                 device="cuda", shard: str = "windows", gather: str = "device", mem_budget: int | None = None,
+                 self_ensemble: bool = False):
         """`shard`: "windows" runs rs.py's windows (dealt longest-processing-time-first over
         ranks, shard_tiles; the canvas equals the single-rank one bit for bit); "bands" runs
         full-width horizontal bands with the same halo (plan_bands: one rank's share is one or a
@@ -324,7 +346,16 @@ class TileUpscaler:
         `mem_budget` (bytes; default: the device's free memory when the image arrives, device_budget)
         bounds every forward: bands / blocks are sized so that one fits, and a shape's `batch` is cut
         to as many tiles as fit together (forward_bytes) — ADVICE r5: the 2 GiB plane window alone
-        would allow a ~250 GiB forward."""
+        would allow a ~250 GiB forward.
+        `self_ensemble` (the "+" of EDSR+): every group of tiles runs as its eight dihedral copies
+        (dihedral.expand_u8: two batches of 4 x the group, the odd members transposed), through
+        `runner.run_f32` (uint8 -> fp32 tanh output; a runner without it is a TypeError here), and
+        dihedral.reduce takes each member back, averages the eight in fp32 and quantises ONCE; crop,
+        stitch, shards and gathers then see uint8 tiles as before.  `batch` still counts tiles per group;
+        the memory rule uses ensemble_forward_bytes.  8 x the forward's cost: for stills."""
+        if self_ensemble and not callable(getattr(runner, "run_f32", None)):
+            raise TypeError(f"self_ensemble needs a runner with run_f32 (uint8 batch -> fp32 tanh output), which "
+                            f"{type(runner).__name__} has not")
         if batch < 1:
             raise ValueError("batch must be >= 1")
         if shard not in ("windows", "bands", "blocks"):
@@ -338,6 +369,7 @@ class TileUpscaler:
         self.shard = shard
         self.gather = gather
         self.mem_budget = mem_budget
+        self.self_ensemble = bool(self_ensemble)
         self.n_scalers = max(0, int(scale).bit_length() - 1)
 
     def _budget(self) -> int | None:
@@ -364,12 +396,15 @@ class TileUpscaler:
         for (h, w), lst in groups.items():
             # windows, bands and blocks of one input shape share a batched forward, as many as fit
             step = self.batch
-            if budget is not None:
+            if budget is not None and self.self_ensemble:
+                while step > 1 and ensemble_forward_bytes(step, h, w, self.n_scalers) > budget:
+                    step -= 1
+            elif budget is not None:
                 step = max(1, min(step, budget // max(1, forward_bytes(1, h, w, self.n_scalers))))
             for i in range(0, len(lst), step):
                 chunk = lst[i:i + step]
                 x = torch.stack([image[:, t.y0:t.y1, t.x0:t.x1] for t in chunk])
-                y = self.runner(x)
+                y = self._ensembled(x) if self.self_ensemble else self.runner(x)
                 if tuple(y.shape) != (len(chunk), 3, h * s, w * s):
                     raise RuntimeError(f"runner returned {tuple(y.shape)} for a {len(chunk)}x3x{h}x{w} batch "
                                        f"at scale {s}")
@@ -377,6 +412,11 @@ class TileUpscaler:
                     oy, ox = (t.y - t.y0) * s, (t.x - t.x0) * s
                     out[t.index] = y[j, :, oy:oy + t.h * s, ox:ox + t.w * s]
         return out
+
+    def _ensembled(self, x: torch.Tensor) -> torch.Tensor:
+        """uint8 tiles -> uint8 outputs through the eight dihedral members (the class docstring)."""
+        even, odd = dihedral.expand_u8(x)
+        return dihedral.reduce(self.runner.run_f32(even), self.runner.run_f32(odd), out_u8=True)
 
     def __call__(self, image: torch.Tensor, rank: int = 0, world: int = 1, group=None) -> torch.Tensor | None:
         """Upscale a uint8 [3,H,W] image.  With world > 1 (torch.distributed

@@ -904,6 +904,69 @@ typedef struct isr_yuv16_desc {
 int isr_yuv420_to_rgb_16(const isr_yuv16_desc* d, isr_stream_t s);
 int isr_rgb_to_yuv420_16(const isr_yuv16_desc* d, isr_stream_t s);
 
+/* ---- dihedral transforms: the eight flips and rotations of an image -------------
+ * An op id is k = r + 4 f with r in 0..3 and f in {0, 1}: with f set, first mirror the image along its
+ * width (column j <-> column w - 1 - j); then turn it r quarter turns counter-clockwise.  An odd r swaps
+ * height and width.  With x the h x w source and y the result, y[i][j] is
+ *   k = 0  x[i][j]                 (h x w)      k = 4  x[i][w - 1 - j]            (h x w)
+ *   k = 1  x[j][w - 1 - i]         (w x h)      k = 5  x[j][i]                    (w x h, the transpose)
+ *   k = 2  x[h - 1 - i][w - 1 - j] (h x w)      k = 6  x[h - 1 - i][j]            (h x w)
+ *   k = 3  x[h - 1 - j][i]         (w x h)      k = 7  x[h - 1 - j][w - 1 - i]    (w x h)
+ * The inverse of k is (4 - k) % 4 for k < 4 and k itself for k >= 4 (a reflection undoes itself):
+ * isr_dihedral_inverse (host only; ISR_ERR_BAD_DESC for k outside 0..7, which sets isr_last_error()).
+ * Values are moved, never changed: every entry point below is exact.
+ *
+ * isr_dihedral: x [n][c][h][w] -> y [n][c][h'][w'], elements of `elem` bytes (1: uint8, 4: fp32 or any
+ * other 4-byte type).  With ops == NULL every image takes the uniform `op` (0..7, else
+ * ISR_ERR_UNSUPPORTED).  With ops a DEVICE array int32 [n], image i takes ops[i] & 7 (any value is
+ * therefore safe; it is never read on the host) and h == w is required (ISR_ERR_UNSUPPORTED otherwise:
+ * the results would not share a shape).  One launch on `s`, no workspace, no synchronisation.
+ * Refused before any launch: a null descriptor, null x or y, x == y (ISR_ERR_BAD_DESC); x, y not
+ * aligned to elem bytes, ops not 4-byte aligned (ISR_ERR_BAD_DESC); n or c outside [1, 65535], h or
+ * w < 1 (ISR_ERR_BAD_DESC); h * w >= 2^31 or more than 2^31 - 1 workgroups (ISR_ERR_UNSUPPORTED); elem
+ * other than 1 or 4 (ISR_ERR_UNSUPPORTED).  uint8 planes that are 4-byte aligned with w and h multiples of
+ * 4 take dword loads and stores; any other shape and alignment is served bytewise at the ragged places. */
+typedef struct isr_dihedral_desc {
+    int32_t n, c, h, w;  /* the source's shape */
+    int32_t elem;        /* bytes per element: 1 or 4 */
+    int32_t op;          /* the uniform op, 0..7 (read when ops is NULL) */
+    const int32_t* ops;  /* device, [n], or NULL */
+    const void* x;
+    void* y;
+} isr_dihedral_desc;
+int isr_dihedral(const isr_dihedral_desc* d, isr_stream_t s);
+int isr_dihedral_inverse(int op);
+
+/* isr_ensemble_expand_u8: the eight transformed copies of each image of x uint8 [n][3][h][w], in one
+ * launch.  Member k of image i (op k applied to it) is image (k / 2) * n + i of `even` [4n][3][h][w] for
+ * k = 0, 2, 4, 6 and of `odd` [4n][3][w][h] for k = 1, 3, 5, 7: two batches, because the odd members have
+ * the transposed shape (square images use the same form).  n in [1, 16383] (4n is a batch of the other
+ * entry points); otherwise the rules of isr_dihedral; x, even and odd must be three different buffers. */
+typedef struct isr_ensemble_expand_desc {
+    int32_t n, h, w;
+    const uint8_t* x;
+    uint8_t* even;
+    uint8_t* odd;
+} isr_ensemble_expand_desc;
+int isr_ensemble_expand_u8(const isr_ensemble_expand_desc* d, isr_stream_t s);
+
+/* isr_ensemble_reduce: the self-ensemble's average.  even fp32 [4n][3][h][w] and odd fp32 [4n][3][w][h]
+ * hold a network's outputs (tanh range, [-1, 1]) for the members in isr_ensemble_expand_u8's order, at the
+ * OUTPUT size h x w.  Per output element the eight members are read where the inverse op of each puts
+ * that element, added in fp32 in the fixed order s = m0; s = s + m1; ...; s = s + m7, and m = s * 0.125f.
+ * y_u8 == 0 stores m as fp32 [n][3][h][w]; otherwise uint8 with the generator tail's own expression,
+ * q = rintf((m + 1.f) / 2.f * 255.f) (ties to even), clamped to [0, 255].  No atomics and no workspace:
+ * the result is the same bits on every run.  even and odd must be 4-byte aligned (16-byte aligned rows
+ * take 16-byte loads), y aligned to its element; n in [1, 16383]; otherwise the rules of isr_dihedral. */
+typedef struct isr_ensemble_reduce_desc {
+    int32_t n, h, w;  /* the output's shape */
+    const float* even;
+    const float* odd;
+    void* y;
+    int32_t y_u8;
+} isr_ensemble_reduce_desc;
+int isr_ensemble_reduce(const isr_ensemble_reduce_desc* d, isr_stream_t s);
+
 const char* isr_last_error(void);
 int isr_version(void);
 

@@ -14,6 +14,11 @@ dealt across ranks and rank 0 writes the image.
 same size on the device and prints one JSON line (psnr, psnr_y, ssim_y; `--ref_border` pixels
 cropped from every side, default 4; metrics.image_metrics).
 
+`--self_ensemble` (image branch) runs every tile as its eight flipped and rotated copies, takes each
+fp32 output back and averages them before the only rounding to 8 bits (the "+" of EDSR+; 8 x the forward's
+cost, tiler.TileUpscaler(self_ensemble=True)); `--ref` then measures the ensembled still.  A video source
+refuses the flag.
+
 `--model` takes a checkpoint written by this package's train.py (state_dicts,
 loaded with weights_only=True) or a state_dict / .safetensors file; the
 reference's TorchScript export is not executed.
@@ -172,7 +177,9 @@ def runer(**kw):
     if kw.get("wino") is not None:  # the default of every pack / plan below (else ISR_WINO, else off)
         from image_super_resolution_amd import engine
         engine.WINO_DEFAULT = engine.wino_mode(kw["wino"])
-    if src.suffix.lower() in VID_FORMATS + RAW_FORMATS + YUV_FORMATS:
+    if is_video(kw["src"]):
+        if kw.get("self_ensemble"):
+            raise ValueError(SELF_ENSEMBLE_VIDEO.format(src=src))
         if not torch.cuda.is_available():
             raise RuntimeError("rs.py runs the HIP generator and needs a GPU")
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -193,7 +200,7 @@ def runer(**kw):
     runner = tiler.runner_for(model, device)
     up = tiler.TileUpscaler(runner, runner.scale, window=kw["window_size"], halo=kw["halo"],
                             batch=kw["batch_size"], device=device, shard=kw.get("shard", "windows"),
-                            gather=kw.get("gather", "device"))
+                            gather=kw.get("gather", "device"), self_ensemble=bool(kw.get("self_ensemble")))
     image = read_image(src)
     ref = None
     if kw.get("ref"):  # every rank checks, so a refusal ends them all
@@ -214,6 +221,23 @@ def runer(**kw):
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
+
+
+SELF_ENSEMBLE_VIDEO = ("--self_ensemble is for stills: {src} is a video source, and eight forwards per frame is "
+                       "not a video feature")
+
+
+def is_video(src: str) -> bool:
+    return Path(src).suffix.lower() in VID_FORMATS + RAW_FORMATS + YUV_FORMATS
+
+
+def parse(argv=None):
+    """The parsed command line; what the flags rule out together is refused here, before any work."""
+    p = build_parser()
+    opt = p.parse_args(argv)
+    if opt.self_ensemble and is_video(opt.src):
+        p.error(SELF_ENSEMBLE_VIDEO.format(src=opt.src))
+    return opt
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -240,6 +264,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "runs per conv (default off, or ISR_WINO)")
     p.add_argument("--ref", type=str, default="", help="ground-truth image of the output's size: after the still "
                    "is written, print one JSON line with its PSNR / PSNR-Y / SSIM-Y against it (image branch)")
+    p.add_argument("--self_ensemble", action="store_true",
+                   help="image branch: average the outputs of the 8 flipped / rotated copies of every tile in fp32 "
+                        "before the only rounding (geometric self-ensemble, 8 x the cost); refused for video")
     p.add_argument("--ref_border", type=int, default=4, help="pixels cropped from every side before the metrics")
     p.add_argument("--pix_fmt", choices=("rgb24", "yuv420p", "nv12", "yuv420p10le", "p010le"), default="rgb24",
                    help="video through ffmpeg: the frames piped from the decoder and to the encoder (rgb24: rgb24 in, "
@@ -258,4 +285,4 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 if __name__ == "__main__":
-    runer(**vars(build_parser().parse_args()))
+    runer(**vars(parse()))

@@ -20,6 +20,9 @@ Pillow's antialiased filters (bicubic, ...: Image.resize bit for bit, one HIP la
 (image_reader's per-sample mix); the val_*.jsonl line records it.  `--lr_degrade blur|blind` degrades
 a copy of the HR crop before that resize, for training only (data.LRDegrade: blur alone, or the
 reference's commented ISONoise / JPEG / blur / GaussNoise chain); validation stays on the undegraded LR.
+`--augment flip|dihedral` mirrors, or mirrors and turns by quarter turns, every training crop at random before
+anything else is made from it (data.GPUTransform / NoisyTransform `augment`, one HIP launch; every mode,
+`--train_denoise` included); validation is never augmented.
 Every mode trains on the HIP path: ResNet (train-mode BatchNorm kernels)
 and EResNet (`--enchant`) in `--resnet` pixel-loss mode and in SRGAN mode (VGG
 perceptual + adversarial, discriminator on libisr), and the Denoise model
@@ -127,6 +130,11 @@ def val_batches(opt, device) -> list:
 def lr_filter_of(opt) -> str:
     """--lr_filter of a parsed command line; "cv2" (SR_dataset's resize) when the flag was not given."""
     return getattr(opt, "lr_filter", "cv2")
+
+
+def augment_of(opt) -> str:
+    """--augment of a parsed command line; "none" when the flag was not given."""
+    return getattr(opt, "augment", "none")
 
 
 def lr_degrade_of(opt, device, seed: int):
@@ -323,7 +331,7 @@ def main(opt):
         if degrade_mode not in ("", "gauss", "reference"):
             raise ValueError(f"ISR_DENOISE_DEGRADE={degrade_mode!r}: '' / 'gauss' (GaussNoise only) or 'reference'")
         make_transform = data.NoisyTransform.reference if degrade_mode == "reference" else data.NoisyTransform
-        transform = make_transform(mean, std, device=device, seed=opt.seed * 7 + rank)
+        transform = make_transform(mean, std, device=device, seed=opt.seed * 7 + rank, augment=augment_of(opt))
         for epoch in range(start, opt.epochs):
             losses = trainer.train(model, ema, batches, transform, nn.MSELoss(), optimizer, scaler_gen, schedule,
                                    epoch, writer, steps=iters)
@@ -338,7 +346,8 @@ def main(opt):
         print(f"Train: ResNet {opt.epochs} epochs, {sum(p.numel() for p in model.parameters()):,} parameters")
         transform = data.GPUTransform(opt.scale, hr_norm=False, mean=mean, std=std, device=device,
                                       lr_filter=lr_filter_of(opt), seed=opt.seed + rank,
-                                      degrade=lr_degrade_of(opt, device, opt.seed * 13 + rank))
+                                      degrade=lr_degrade_of(opt, device, opt.seed * 13 + rank),
+                                      augment=augment_of(opt))
         val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, res_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train(model, ema, batches, transform, compute_loss, optimizer, scaler_gen, schedule,
@@ -360,7 +369,8 @@ def main(opt):
               f"dis {sum(p.numel() for p in dis_net.parameters()):,} parameters")
         transform = data.GPUTransform(opt.scale, hr_norm=True, mean=mean, std=std, device=device,
                                       lr_filter=lr_filter_of(opt), seed=opt.seed + rank,
-                                      degrade=lr_degrade_of(opt, device, opt.seed * 13 + rank))
+                                      degrade=lr_degrade_of(opt, device, opt.seed * 13 + rank),
+                                      augment=augment_of(opt))
         val = _Validation(opt, device, work_dir, rank, group, writer, mean, std, gen_ck) if validating else None
         for epoch in range(start, opt.epochs):
             losses = trainer.train_srgan(gen_net, ema, dis_net, batches, transform, compute_loss, optimizer_g,
@@ -440,6 +450,10 @@ def parse(argv=None):
                    help="degrade a copy of the HR crop before the LR resize (training only; validation keeps the "
                    "undegraded LR): blur (box / Gaussian / motion / median blur, k in 3, 5, 7, p = 0.5) or blind (the "
                    "reference's commented chain: ISONoise 0.05, JPEG 0.1 at quality 45..75, blur 0.3, GaussNoise 0.1)")
+    p.add_argument("--augment", default=argparse.SUPPRESS, choices=data.AUGMENTS,
+                   help="geometric augmentation of the training crops, per image and on the device (validation is "
+                   "never augmented): flip (a mirror along the width with probability 0.5) or dihedral (one of the 8 "
+                   "flips and quarter turns, uniform); absent means none")
     opt = p.parse_args(argv)
     if opt.val_every < 1:
         p.error("--val_every must be at least 1")
