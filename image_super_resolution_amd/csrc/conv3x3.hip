@@ -52,76 +52,66 @@ __device__ __forceinline__ void conv_stamp(int slot) {
 #endif
 }
 
-template <int R_, int WM_, int NF_, int KC_, int NST_, int CIN_ = 0, int ABL_ = 0, int PIPE_ = (NF_ == 1), int EPQ_ = 4,
-          int SPL_ = 0, int TWN_ = 0, int NSW_ = 0, int FOLD_ = 0, int H_ = 0>
-struct C3 {
-    static constexpr int R = R_, WM = WM_, NF = NF_, KC = KC_, NST = NST_;
-    // storage type of activations and weights: 0 = bf16, 1 = fp16 (isr_conv_desc.f16, inference)
-    static constexpr bool H = H_ != 0;
+// Knobs of one tile configuration, with their defaults: a named configuration (K_* below) derives
+// from this and shadows the knobs in which it differs; C3<K> adds everything that follows from them.
+struct C3Knobs {
+    // output rows per wave, waves per block, 32-cout fragments per block, input channels per
+    // chunk (16 or 32), chunk ring depth
+    static constexpr int R = 4, WM = 4, NF = 1, KC = 16, NST = 2;
+    // storage type of activations and weights: false = bf16, true = fp16 (isr_conv_desc.f16, inference)
+    static constexpr bool H = false;
     // 1: the RDB residual fold (r1 == the conv's own input channels, see fold_ok) is compiled in;
     // only the RDB final-conv instantiations carry it (it costs registers)
-    static constexpr int FOLD = FOLD_;
-    // 1: double-buffered fragment registers across (k-step, dx) steps; 2: the next step's reads
-    // spread over the current step's MFMAs (front-loading them instead: 0.43-0.92x, register
-    // pressure)
-    static constexpr int PIPE = PIPE_;
-    static constexpr int EPQ = EPQ_;   // epilogue operand units (8 VGPRs each) loaded per pass
-    // refill placement: 0 = the next chunk's LDS-DMA issued right after the current chunk's
-    // step-0 fragment reads (PIPE 2; otherwise as 1), 1 = issued before them (round-1 order),
-    // > 1 = issued in SPL parts, one before each of the first SPL steps
-    static constexpr int SPL = SPL_;
+    static constexpr int FOLD = 0;
+    // 0: each step's fragments read right before its MFMAs; 1: double-buffered fragment registers
+    // across (k-step, dx) steps; 2: the next step's reads spread over the current step's MFMAs
+    // (front-loading them instead: 0.43-0.92x, register pressure)
+    static constexpr int PIPE = 0;
+    // refill placement with PIPE 2: false = the next chunk's LDS-DMA issued right after the current
+    // chunk's step-0 fragment reads, true = issued before them (round-1 order; as without PIPE 2)
+    static constexpr bool REFILL_FIRST = false;
     // tap window: 0 = all 3x3 taps; 1 = taps {0,1}^2; 2 = taps {1,2}^2 (the 2x2 convs that a
     // stride-2 3x3 conv and its transpose become on the 2x2 phase decomposition, isr_conv_desc.taps)
-    static constexpr int TWN = TWN_;
-    static constexpr int TLO = TWN == 2 ? 1 : 0;
-    static constexpr int TN = TWN ? 2 : 3;
-    static constexpr int NA = R + TN - 1;  // input rows one wave reads per step
-    static constexpr int CIN = CIN_; // 0 = runtime cin; else compile-time (own symbol)
+    static constexpr int TWN = 0;
+    static constexpr int CIN = 0; // 0 = runtime cin; else compile-time (own symbol)
     // Ablation bits, tuning builds only (outputs wrong): 1 = no MFMA (operands
     // kept live), 2 = stage only chunk 0 (no refill), 4 = no epilogue stores, 8 = the weights of
     // chunk 0 only (later chunks refill their halo but not their weights: the time a block would
     // take with its weights resident in LDS, round 6 probe for the Scaler / VGG short-K convs).
-    static constexpr int ABL = ABL_;
-    static constexpr int TH = R * WM;
+    static constexpr int ABL = 0;
+};
+
+template <class K>
+struct C3 : K {
+    static constexpr int TLO = K::TWN == 2 ? 1 : 0;
+    static constexpr int TN = K::TWN ? 2 : 3;
+    static constexpr int NA = K::R + TN - 1;  // input rows one wave reads per step
+    static constexpr int TH = K::R * K::WM;
     static constexpr int TW = 32;
     static constexpr int HR = TH + 2;  // halo rows
     static constexpr int HC = TW + 2;  // halo cols
-    static constexpr int CT = NF * 32; // output channels per block
-    static constexpr int KS = KC / 16; // MFMA k-steps (= planes) per chunk
+    static constexpr int CT = K::NF * 32; // output channels per block
+    static constexpr int KS = K::KC / 16; // MFMA k-steps (= planes) per chunk
     static constexpr int HQ = HR * HC; // halo pixels per plane
     static constexpr int HIPL = (HQ + 31) / 32; // glds instructions per plane (32 px x 32 B each)
     static constexpr int HALO_INSTR = KS * HIPL;
     static constexpr int W_INSTR = 9 * KS * CT / 32; // [ks][tap][n][hpos] x 16 B
     static constexpr int INSTR = HALO_INSTR + W_INSTR;
-    static constexpr int IPW = (INSTR + WM - 1) / WM; // glds per wave per chunk (uniform)
-    static constexpr int STAGE = IPW * WM * 1024;
-    // NSW > 0: separate rings — halo planes NST deep (NST-1 chunks in flight), weights NSW deep
-    // (one chunk ahead): the growth convs keep two halo chunks in flight at two blocks per CU
-    static constexpr int NSW = NSW_;
-    static constexpr int IPWH = (HALO_INSTR + WM - 1) / WM; // halo glds per wave per chunk
-    static constexpr int IPWW = (W_INSTR + WM - 1) / WM;    // weight glds per wave (the last
-                                                            // round repeats pieces: same bytes)
-    static constexpr int HSTAGE = HALO_INSTR * 1024;
-    static constexpr int WSTAGE = W_INSTR * 1024;
-    static constexpr int RING = NSW ? NST * HSTAGE + NSW * WSTAGE : NST * STAGE;
-    static constexpr int NT = 64 * WM;
+    static constexpr int IPW = (INSTR + K::WM - 1) / K::WM; // glds per wave per chunk (uniform)
+    static constexpr int STAGE = IPW * K::WM * 1024;
+    static constexpr int RING = K::NST * STAGE;
+    static constexpr int NT = 64 * K::WM;
     static constexpr int EPS = CT + 4;                 // floats per pixel in the epilogue image
-    static constexpr int EP_BYTES = WM * 32 * EPS * 4; // one output row per wave at a time
+    static constexpr int EP_BYTES = K::WM * 32 * EPS * 4; // one output row per wave at a time
     static constexpr int LDS = (RING > EP_BYTES) ? RING : EP_BYTES;
-    static_assert(!NSW || (HALO_INSTR % WM == 0 && NST >= 3 && NSW == 2), "split rings");
     static constexpr int BPC = 163840 / LDS; // blocks per CU by LDS
-    static constexpr int OCC = BPC * WM / 4 >= 2 ? 2 : 1; // waves per SIMD to budget registers for
+    static constexpr int OCC = BPC * K::WM / 4 >= 2 ? 2 : 1; // waves per SIMD to budget registers for
     static_assert(LDS <= 163840, "LDS budget");
-    static_assert(KC == 16 || KC == 32, "chunk width");
+    static_assert(K::KC == 16 || K::KC == 32, "chunk width");
+    static_assert(!K::REFILL_FIRST || K::PIPE == 2, "REFILL_FIRST picks between the two orders of PIPE 2");
 };
 
 template <int V> struct IC { static constexpr int value = V; };
-
-// 1: s_setprio 1 around each chunk's MFMA steps (as the trunk kernel): measured slower on the
-// SRGAN step, 54.43 / 54.53 vs 53.95 / 54.21 ms same box (profiles/r03_train_conv_prio_ab.jsonl)
-#ifndef ISR_CONV_PRIO
-#define ISR_CONV_PRIO 0
-#endif
 
 // A operand of the residual fold: (1/s1) I on couts [16 h16, 16 h16 + 16) of a 32-cout
 // fragment (lane l supplies A[l & 31][8 (l >> 5) .. + 8]); trunk.hip builds the same.
@@ -234,7 +224,7 @@ __device__ __forceinline__ void epilogue(const isr_conv_desc& d, f32x16 (&acc)[C
         // Loads of a unit precede its stores (in-place RRDB update: y may alias r1/r2).
         constexpr int P = ((MODE & 1) ? 1 : 0) + ((MODE & 2) ? 1 : 0) + ((MODE & 16) ? 1 : 0);
         constexpr int NU = R * NF;
-        constexpr int U0 = P == 0 ? 1 : (C::EPQ / P > 0 ? C::EPQ / P : 1);
+        constexpr int U0 = P == 0 ? 1 : 4 / P;  // 4 operand units (8 VGPRs each) loaded per pass
         constexpr int U = U0 > NU ? NU : U0;
         static_assert(NU % U == 0, "units per pass");
         bf16x8 q1[U][2], q2[U][2], qm[U][2];
@@ -379,36 +369,12 @@ __device__ __forceinline__ void conv_tile(const isr_conv_desc& d, int t) {
         return o;
     };
 
-    // split rings (NSW): halo pieces j = wave + WM*k (k < IPWH) and weight pieces jj = (wave + WM*k) %
-    // W_INSTR (k < IPWW; the wrap repeats a piece: the same bytes to the same LDS address)
-    auto stage_h = [&](int chunk, int buf) {
-        char* dst = smem + buf * C::HSTAGE;
-        const char* xs = xbase + xchunk(chunk);
-#pragma unroll
-        for (int k = 0; k < C::IPWH; ++k) {
-            const int j = wave + WM * k;
-            const uint32_t o = off_of(k);
-            glds16(xs + o, dst + j * 1024);
-        }
-    };
-    auto stage_w = [&](int chunk, int buf) {
-        char* dst = smem + C::NST * C::HSTAGE + buf * C::WSTAGE;
-        const char* ws = wbase + (size_t)chunk * wchunk_bytes;
-#pragma unroll
-        for (int k = 0; k < C::IPWW; ++k) {
-            const int jj = (wave + WM * k) % C::W_INSTR;
-            const int u = jj * 64 + lane;
-            const int seg = u / (C::CT * 2);
-            const int rem = u - seg * (C::CT * 2);
-            glds16(ws + (uint32_t)((seg * d.cout + ct * C::CT) * 32 + rem * 16), dst + jj * 1024);
-        }
-    };
-    auto stage = [&](int chunk, int buf, int k0 = 0, int k1 = C::IPW) {
+    auto stage = [&](int chunk, int buf) {
         char* dst = smem + buf * C::STAGE;
         const char* xs = xbase + xchunk(chunk);
         const char* ws = wbase + (size_t)chunk * wchunk_bytes;
 #pragma unroll
-        for (int k = k0; k < k1; ++k) {
+        for (int k = 0; k < C::IPW; ++k) {
             const int j = wave + WM * k;
             const uint32_t o = off_of(k);
             if (j < C::HALO_INSTR) {
@@ -433,17 +399,9 @@ __device__ __forceinline__ void conv_tile(const isr_conv_desc& d, int t) {
     }
 
     auto prologue = [&]() {
-        if constexpr (C::NSW) {  // issue order h(0), w(0), h(1), ..., h(NST-2): see the chunk wait
-            stage_h(0, 0);
-            stage_w(0, 0);
 #pragma unroll
-            for (int s = 1; s < C::NST - 1; ++s)
-                if (s < nchunks) stage_h(s, s);
-        } else {
-#pragma unroll
-            for (int s = 0; s < C::NST - 1; ++s)
-                if (s < nchunks) stage(s, s);
-        }
+        for (int s = 0; s < C::NST - 1; ++s)
+            if (s < nchunks) stage(s, s);
     };
     prologue();
     conv_stamp(5);
@@ -456,16 +414,7 @@ __device__ __forceinline__ void conv_tile(const isr_conv_desc& d, int t) {
         constexpr int FC = decltype(fc_tag)::value;
         (void)FC;
             // chunk `chunk` landed for this wave: younger chunks in flight = min(NST-2, nchunks-1-chunk)
-            if constexpr (C::NSW) {
-                // issue order ... w(c-1) h(c+1) | w(c) h(c+2) ...: at chunk c only the halo pieces of
-                // chunk c+1 (issued after w(c)) may still be in flight (NST == 3)
-                static_assert(C::NSW == 0 || C::NST == 3, "split-ring wait assumes NST 3");
-                if (chunk + 1 < nchunks) {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::IPWH) : "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-            } else if constexpr (C::NST >= 3) {
+            if constexpr (C::NST >= 3) {
                 if (chunk + C::NST - 2 < nchunks) {
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((C::NST - 2) * C::IPW) : "memory");
                 } else {
@@ -478,20 +427,12 @@ __device__ __forceinline__ void conv_tile(const isr_conv_desc& d, int t) {
             __builtin_amdgcn_s_barrier();
             if (chunk == 0) conv_stamp(1);
             const bool refill = !(C::ABL & 2) && chunk + C::NST - 1 < nchunks;
-            // split rings: w(chunk+1) then h(chunk+NST-1), each when it exists
-            auto refill_split = [&]() {
-                if (chunk + 1 < nchunks) stage_w(chunk + 1, (chunk + 1) % C::NSW);
-                if (refill) stage_h(chunk + C::NST - 1, (chunk + C::NST - 1) % C::NST);
-            };
-            if constexpr (C::SPL == 1 || (C::SPL == 0 && C::PIPE != 2)) {
-                if constexpr (C::NSW) refill_split();
-                else if (refill) stage(chunk + C::NST - 1, (chunk + C::NST - 1) % C::NST);
+            if constexpr (C::REFILL_FIRST || C::PIPE != 2) {
+                if (refill) stage(chunk + C::NST - 1, (chunk + C::NST - 1) % C::NST);
             }
 
-            const char* hs = C::NSW ? smem + (chunk % C::NST) * C::HSTAGE
-                                    : smem + ((C::ABL & 2) ? 0 : (chunk % C::NST)) * C::STAGE;
-            const char* ws = C::NSW ? smem + C::NST * C::HSTAGE + (chunk % (C::NSW ? C::NSW : 1)) * C::WSTAGE
-                                    : hs + C::HALO_INSTR * 1024;
+            const char* hs = smem + ((C::ABL & 2) ? 0 : (chunk % C::NST)) * C::STAGE;
+            const char* ws = hs + C::HALO_INSTR * 1024;
             // Software pipeline over the chunk's (k-step, dx) steps: the fragments of
             // step st+1 are read into the other register set while step st's MFMAs
             // run, so LDS latency is covered by MFMA work of the same wave.
@@ -538,24 +479,14 @@ __device__ __forceinline__ void conv_tile(const isr_conv_desc& d, int t) {
                 // the refill's LDS-DMA issue (10-16 instructions, scalar address math) runs while
                 // step 0's fragment reads are in flight, instead of ahead of them
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (C::SPL == 0) {
-                    if constexpr (C::NSW) refill_split();
-                    else if (refill) stage(chunk + C::NST - 1, (chunk + C::NST - 1) % C::NST);
+                if constexpr (!C::REFILL_FIRST) {
+                    if (refill) stage(chunk + C::NST - 1, (chunk + C::NST - 1) % C::NST);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-    #if ISR_CONV_PRIO
-            __builtin_amdgcn_s_setprio(1);  // A/B: the MFMA steps ahead of the co-resident block's issue
-#endif
 #pragma unroll
             for (int st = 0; st < NS; ++st) {
                 const int cur = C::PIPE ? (st & 1) : 0;
-                if constexpr (C::SPL > 1) {
-                    static_assert(C::SPL <= NS, "refill parts must fit the chunk's steps");
-                    if (st < C::SPL && refill)
-                        stage(chunk + C::NST - 1, (chunk + C::NST - 1) % C::NST, st * C::IPW / C::SPL,
-                              (st + 1) * C::IPW / C::SPL);
-                }
                 if constexpr (C::PIPE == 2) {
                     // interleaved: this step's MFMAs with the next step's fragment reads (one
                     // read after each MFMA), so at most one step's reads are in flight (<= 15,
@@ -619,9 +550,6 @@ __device__ __forceinline__ void conv_tile(const isr_conv_desc& d, int t) {
                     }
                 }
             }
-#if ISR_CONV_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
     };
     int chunk0 = 0;
     if constexpr (C::FOLD && C::NF == 2 && C::KS == 1 && C::TN == 3) {
@@ -714,25 +642,45 @@ static int launch3x3(const isr_conv_desc* d, hipStream_t s) {
 // kept for on-device A/B tuning (isr_conv3x3_fwd_variant, tools/tune_conv.py).
 // (tools/tune_conv.py on MI355X, N=16 128²: the 16x32-tile, 2-blocks/CU configs are
 // fastest on every shape of the generator; the 32x32 8-wave tiles win only at long K)
-// cout == 32 (RDB growth convs)
+// A K_* record spells the knobs in which it differs from C3Knobs (or from the record it derives
+// from); V_* = C3<K_*> are the production tiles.
 // V_G0 / V_F0: the next step's fragment reads interleaved one per MFMA (PIPE 2): 2-7 % over the
 // batched prefetch, whose 18-24 reads in flight exceed lgkmcnt's range (so hipcc waited lgkmcnt(0))
-using V_G0 = C3<4, 4, 1, 16, 2, 0, 0, 2>; // 16x32, 4 waves, KC16 double buffer, 58 KB → 2 blocks / CU
-using V_G1 = C3<4, 8, 1, 16, 3>; // 32x32 px tile, 8 waves, 3-deep KC16 ring
-using V_G2 = C3<2, 4, 1, 32, 2>; // 8x32, KC32, 2 blocks / CU
-using V_G3 = C3<2, 4, 1, 16, 2, 0, 0, 2>; // 8x32 tile, double buffer, interleaved
-// cout % 64 == 0
-using V_W0 = C3<4, 4, 2, 16, 2, 0, 0, 2>; // 16x32, 4 waves, KC16 double buffer, 76 KB → 2 blocks / CU, PIPE 2
-using V_W1 = C3<4, 8, 2, 16, 2>; // 32x32 px tile, 8 waves, KC16 double buffer
-using V_W2 = C3<2, 4, 2, 32, 2>; // 8x32, KC32
-using V_W3 = C3<2, 4, 2, 16, 2, 0, 0, 2>; // 8x32 tile, interleaved
-using V_F0 = C3<4, 4, 2, 16, 2, 192, 0, 2>; // RDB final conv 192→64: V_W0 with compile-time cin, PIPE 2
-using V_F0F = C3<4, 4, 2, 16, 2, 192, 0, 2, 4, 0, 0, 0, 1>; // V_F0 with the residual fold (r1 == x)
+// cout == 32 (RDB growth convs): 16x32, 4 waves, KC16 double buffer, 58 KB → 2 blocks / CU
+struct K_G0 : C3Knobs { static constexpr int PIPE = 2; };
+// cout % 64 == 0: 16x32, 4 waves, KC16 double buffer, 76 KB → 2 blocks / CU
+struct K_W0 : C3Knobs { static constexpr int NF = 2, PIPE = 2; };
+struct K_F0 : K_W0 { static constexpr int CIN = 192; };  // RDB final conv 192→64: V_W0 with compile-time cin
+struct K_F0F : K_F0 { static constexpr int FOLD = 1; };  // V_F0 with the residual fold (r1 == x)
 // fp16 storage (isr_conv_desc.f16: the inference path) — the same four production tiles
-using V_G0H = C3<4, 4, 1, 16, 2, 0, 0, 2, 4, 0, 0, 0, 0, 1>;
-using V_W0H = C3<4, 4, 2, 16, 2, 0, 0, 2, 4, 0, 0, 0, 0, 1>;
-using V_F0H = C3<4, 4, 2, 16, 2, 192, 0, 2, 4, 0, 0, 0, 0, 1>;
-using V_F0FH = C3<4, 4, 2, 16, 2, 192, 0, 2, 4, 0, 0, 0, 1, 1>;
+struct K_G0H : K_G0 { static constexpr bool H = true; };
+struct K_W0H : K_W0 { static constexpr bool H = true; };
+struct K_F0H : K_F0 { static constexpr bool H = true; };
+struct K_F0FH : K_F0F { static constexpr bool H = true; };
+// tap windows {0,1}^2 / {1,2}^2 (isr_conv_desc.taps 1 / 2): the V_W0 tile without the fragment pipeline
+struct K_T01 : C3Knobs { static constexpr int NF = 2, TWN = 1; };
+struct K_T12 : C3Knobs { static constexpr int NF = 2, TWN = 2; };
+using V_G0 = C3<K_G0>; using V_W0 = C3<K_W0>; using V_F0 = C3<K_F0>; using V_F0F = C3<K_F0F>;
+using V_G0H = C3<K_G0H>; using V_W0H = C3<K_W0H>; using V_F0H = C3<K_F0H>; using V_F0FH = C3<K_F0FH>;
+#ifdef ISR_TUNING  // the A/B variants of conv3x3_fwd_variant (K_G1 / K_G2 prefetch, PIPE 1; K_W1 / K_W2 not)
+struct K_G1 : C3Knobs { static constexpr int WM = 8, NST = 3, PIPE = 1; };  // 32x32 px tile, 8 waves, 3-deep KC16 ring
+struct K_G2 : C3Knobs { static constexpr int R = 2, KC = 32, PIPE = 1; };   // 8x32, KC32, 2 blocks / CU
+struct K_G3 : C3Knobs { static constexpr int R = 2, PIPE = 2; };            // 8x32 tile, double buffer, interleaved
+struct K_W1 : C3Knobs { static constexpr int WM = 8, NF = 2; };             // 32x32 px tile, 8 waves, KC16 double buffer
+struct K_W2 : C3Knobs { static constexpr int R = 2, NF = 2, KC = 32; };     // 8x32, KC32
+struct K_W3 : C3Knobs { static constexpr int R = 2, NF = 2, PIPE = 2; };    // 8x32 tile, interleaved
+struct K_G0R : K_G0 { static constexpr bool REFILL_FIRST = true; };  // variant 8: refill before step-0 reads (r1)
+struct K_W0R : K_W0 { static constexpr bool REFILL_FIRST = true; };
+struct K_F0R : K_F0 { static constexpr bool REFILL_FIRST = true; };
+struct K_G0X8 : K_G0 { static constexpr int WM = 8; };  // variant 9: 32x32 tile, 8 waves, PIPE 2 (92 KB, 1 block/CU)
+struct K_W0X8 : K_W0 { static constexpr int WM = 8; };  // (111 KB)
+struct K_F0X8 : K_F0 { static constexpr int WM = 8; };
+struct K_W0NW : K_W0 { static constexpr int ABL = 8; };  // timing probes (outputs wrong): V_W0 / K_W0X8
+struct K_W0X8NW : K_W0X8 { static constexpr int ABL = 8; };  // without the weight refills
+// ablations ABL_ of the V_G0 / V_W0 tiles (timing only, outputs wrong), with PIPE 1 / 0
+template <int ABL_> struct K_GAbl : C3Knobs { static constexpr int PIPE = 1, ABL = ABL_; };
+template <int ABL_> struct K_WAbl : C3Knobs { static constexpr int NF = 2, ABL = ABL_; };
+#endif
 
 // Host mirror of fold_ok: r1 is the conv's own input channels [0, cout), identity activation,
 // 1/s1 exact in bf16 (its low 16 fp32 bits zero).
@@ -761,16 +709,16 @@ int conv3x3_fwd_variant(const isr_conv_desc* d, int variant, hipStream_t s) {
             case 0: return launch3x3<V_G0, true>(d, s);
 #ifdef ISR_TUNING
             // A/B tile configurations (none faster than V_G0 on the generator's shapes)
-            case 1: return launch3x3<V_G1>(d, s);
-            case 2: return launch3x3<V_G2>(d, s);
-            case 3: return launch3x3<V_G3>(d, s);
-            case 8: return launch3x3<C3<4, 4, 1, 16, 2, 0, 0, 2, 4, 1>>(d, s);  // V_G0, refill before step-0 reads (r1)
-            case 9: return launch3x3<C3<4, 8, 1, 16, 2, 0, 0, 2>>(d, s);  // 32x32 tile, 8 waves, PIPE 2 (92 KB, 1 block/CU)
-            // ablations of V_G0 (timing only, outputs wrong): tuning builds only
-            case 4: return launch3x3<C3<4, 4, 1, 16, 2, 0, 1>>(d, s);
-            case 5: return launch3x3<C3<4, 4, 1, 16, 2, 0, 2>>(d, s);
-            case 6: return launch3x3<C3<4, 4, 1, 16, 2, 0, 4>>(d, s);
-            case 7: return launch3x3<C3<4, 4, 1, 16, 2, 0, 3>>(d, s);
+            case 1: return launch3x3<C3<K_G1>>(d, s);
+            case 2: return launch3x3<C3<K_G2>>(d, s);
+            case 3: return launch3x3<C3<K_G3>>(d, s);
+            case 8: return launch3x3<C3<K_G0R>>(d, s);
+            case 9: return launch3x3<C3<K_G0X8>>(d, s);
+            // ablations (timing only, outputs wrong): tuning builds only
+            case 4: return launch3x3<C3<K_GAbl<1>>>(d, s);
+            case 5: return launch3x3<C3<K_GAbl<2>>>(d, s);
+            case 6: return launch3x3<C3<K_GAbl<4>>>(d, s);
+            case 7: return launch3x3<C3<K_GAbl<3>>>(d, s);
 #endif
         }
         return -2;
@@ -779,21 +727,19 @@ int conv3x3_fwd_variant(const isr_conv_desc* d, int variant, hipStream_t s) {
         case 0: return d->cin == 192 ? (fold_host(d) ? launch3x3<V_F0F>(d, s) : launch3x3<V_F0, true>(d, s))
                                      : launch3x3<V_W0, true>(d, s);
 #ifdef ISR_TUNING
-        case 1: return launch3x3<V_W1>(d, s);
-        case 2: return launch3x3<V_W2>(d, s);
-        case 3: return launch3x3<V_W3>(d, s);
-        case 8: return d->cin == 192 ? launch3x3<C3<4, 4, 2, 16, 2, 192, 0, 2, 4, 1>>(d, s)  // refill before reads (r1)
-                                     : launch3x3<C3<4, 4, 2, 16, 2, 0, 0, 2, 4, 1>>(d, s);
-        case 9: return d->cin == 192 ? launch3x3<C3<4, 8, 2, 16, 2, 192, 0, 2>>(d, s)  // 32x32, 8 waves, PIPE 2 (111 KB)
-                                     : launch3x3<C3<4, 8, 2, 16, 2, 0, 0, 2>>(d, s);
+        case 1: return launch3x3<C3<K_W1>>(d, s);
+        case 2: return launch3x3<C3<K_W2>>(d, s);
+        case 3: return launch3x3<C3<K_W3>>(d, s);
+        case 8: return d->cin == 192 ? launch3x3<C3<K_F0R>>(d, s) : launch3x3<C3<K_W0R>>(d, s);
+        case 9: return d->cin == 192 ? launch3x3<C3<K_F0X8>>(d, s) : launch3x3<C3<K_W0X8>>(d, s);
         // timing probes (outputs wrong): V_W0 / variant 9 without the weight refills (ABL 8)
-        case 10: return launch3x3<C3<4, 4, 2, 16, 2, 0, 8, 2>>(d, s);
-        case 11: return launch3x3<C3<4, 8, 2, 16, 2, 0, 8, 2>>(d, s);
-        // ablations of V_W0 (timing only, outputs wrong): tuning builds only
-        case 4: return launch3x3<C3<4, 4, 2, 16, 2, 0, 1>>(d, s);
-        case 5: return launch3x3<C3<4, 4, 2, 16, 2, 0, 2>>(d, s);
-        case 6: return launch3x3<C3<4, 4, 2, 16, 2, 0, 4>>(d, s);
-        case 7: return launch3x3<C3<4, 4, 2, 16, 2, 0, 3>>(d, s);
+        case 10: return launch3x3<C3<K_W0NW>>(d, s);
+        case 11: return launch3x3<C3<K_W0X8NW>>(d, s);
+        // ablations (timing only, outputs wrong): tuning builds only
+        case 4: return launch3x3<C3<K_WAbl<1>>>(d, s);
+        case 5: return launch3x3<C3<K_WAbl<2>>>(d, s);
+        case 6: return launch3x3<C3<K_WAbl<4>>>(d, s);
+        case 7: return launch3x3<C3<K_WAbl<3>>>(d, s);
 #endif
     }
     return -2;
@@ -807,8 +753,8 @@ int conv_stamps_set(void*) { return -2; }
 
 int conv3x3_fwd_dispatch(const isr_conv_desc* d, hipStream_t s) {
     if (d->f16) return conv3x3_fwd_variant(d, 0, s);
-    if (d->taps == 1) return d->cout % 64 ? -2 : launch3x3<C3<4, 4, 2, 16, 2, 0, 0, 0, 4, 1, 1>, true>(d, s);
-    if (d->taps == 2) return d->cout % 64 ? -2 : launch3x3<C3<4, 4, 2, 16, 2, 0, 0, 0, 4, 1, 2>, true>(d, s);
+    if (d->taps == 1) return d->cout % 64 ? -2 : launch3x3<C3<K_T01>, true>(d, s);
+    if (d->taps == 2) return d->cout % 64 ? -2 : launch3x3<C3<K_T12>, true>(d, s);
     return conv3x3_fwd_variant(d, 0, s);
 }
 

@@ -24,6 +24,7 @@
 // layout (and un-permutes the PixelShuffle channel order for g_sub2).
 #include "isr_common.h"
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
 namespace isr {
@@ -69,44 +70,53 @@ __device__ __forceinline__ void sfor(F&& f) {
     sfor_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-template <int NCO_, int NCI_, int TY_, int KW_ = 1, int TWN_ = 0, int CW_ = 1, int NSTG_ = 2, int RS_ = 0, int AR_ = 0>
-struct WG {
-    // AR = 1: the kernel-row form with the asm transposing reads (tr4_at) and counted waits, one
-    // K group read ahead; AR = 2 the same without read-ahead — the same MFMAs in the same order
-    // as AR = 0 (bit-identical)
-    static constexpr int AR = AR_;
-    static constexpr int NCO = NCO_, NCI = NCI_, TY = TY_;
+// Knobs of one tile configuration, with their defaults: a named configuration (K_* below, at the
+// pickers) derives from this and shadows the knobs in which it differs; WG<K> adds what follows.
+struct WGKnobs {
+    // 32-channel co / ci tiles per block, pixel rows per stage
+    static constexpr int NCO = 1, NCI = 1, TY = 4;
+    // KW waves per kernel row dy split each stage's K (pixel groups) between them;
+    // their partial sums are added through LDS before the workspace store
+    static constexpr int KW = 1;
+    // tap window: 0 = 3x3; 1 = taps {0,1}^2 (2 kernel rows, 2 columns: stride-2 phase convs)
+    static constexpr int TWN = 0;
+    // CW waves per (kernel row, K-share) split the block's NCI ci tiles between them: the block
+    // stages each pixel tile's G and X planes ONCE for all its ci tiles (CW = NCI: every 32-ci
+    // tile of the layer in one block, so G is not re-staged per ci tile)
+    static constexpr int CW = 1;
+    // LDS stages in the pixel-tile ring: 2 (stage t+1 lands while stage t computes) or 3 (two
+    // stages in flight: the weight-gradient loop had waited on its staging, PMC wait_any 0.48)
+    static constexpr int NSTG = 2;
     // row sweep (RS = 1): wave w owns kernel COLUMN dx = w % 3 and all three kernel rows, and walks
     // the stage's halo rows once: X row rho is read once and feeds the taps (dy, dx) of G rows
     // rho - dy, dy = 0..2 (the G fragments of the last three rows stay in registers).  Per 3 MFMAs
     // that is one X + one G fragment instead of one G + three X fragments per 3 MFMAs (the
     // default, wave = kernel row): the LDS read stream per MFMA halves.  Same operands, same
-    // per-tap summation order (G rows ascending) -> bit-identical partials.
-    static constexpr int RS = RS_;
-    static_assert(!RS_ || (TWN_ == 0 && KW_ == 2), "row sweep: 3x3 taps, one column half per K-share wave");
-    static_assert(!((RS_ & 2) && (RS_ & 8)), "per-row DMA pieces and loader waves exclude each other");
-    // LDS stages in the pixel-tile ring: 2 (stage t+1 lands while stage t computes) or 3 (two
-    // stages in flight: the weight-gradient loop had waited on its staging, PMC wait_any 0.48)
-    static constexpr int NSTG = NSTG_;
-    // CW waves per (kernel row, K-share) split the block's NCI ci tiles between them: the block
-    // stages each pixel tile's G and X planes ONCE for all its ci tiles (CW = NCI: every 32-ci
-    // tile of the layer in one block, so G is not re-staged per ci tile)
-    static constexpr int CW = CW_, NCIW = NCI_ / CW_;
-    // tap window: 0 = 3x3; 1 = taps {0,1}^2 (2 kernel rows, 2 columns: stride-2 phase convs)
-    static constexpr int TWN = TWN_, TN = TWN_ ? 2 : 3;
-    // KW waves per kernel row dy split each stage's K (pixel groups) between them;
-    // their partial sums are added through LDS before the workspace store
-    static constexpr int KW = KW_;
+    // per-tap summation order (G rows ascending) -> bit-identical partials.  Bits 2 / 4 / 8: A/B
+    // forms of its DMA issue and read-ahead (see the row sweep in wgrad_body, and LW below)
+    static constexpr int RS = 0;
+    // AR = 1: the kernel-row form with the asm transposing reads (tr4_at) and counted waits, one
+    // K group read ahead; AR = 2 the same without read-ahead — the same MFMAs in the same order
+    // as AR = 0 (bit-identical)
+    static constexpr int AR = 0;
+};
+
+template <class K>
+struct WG : K {
+    static_assert(!K::RS || (K::TWN == 0 && K::KW == 2), "row sweep: 3x3 taps, one column half per K-share wave");
+    static_assert(!((K::RS & 2) && (K::RS & 8)), "per-row DMA pieces and loader waves exclude each other");
+    static constexpr int NCIW = K::NCI / K::CW;  // ci tiles per CW wave
+    static constexpr int TN = K::TWN ? 2 : 3;
     // RS & 8: LW = 2 loader waves per block issue every LDS-DMA piece (the compute waves issue
     // none: their reads and MFMAs no longer queue behind ~7 DMA issues per stage)
-    static constexpr int LW = (RS_ & 8) ? 2 : 0;
-    static constexpr int WM = TN * KW * CW, NT = 64 * (WM + LW);
+    static constexpr int LW = (K::RS & 8) ? 2 : 0;
+    static constexpr int WM = TN * K::KW * K::CW, NT = 64 * (WM + LW);
     static constexpr int SW = LW ? LW : WM;  // waves that stage
-    static_assert(NCI % CW == 0, "ci tiles split evenly between the CW waves");
-    static constexpr int CO_T = 32 * NCO, CI_T = 32 * NCI;
-    static constexpr int GPL = 2 * NCO, XPL = 2 * NCI;         // 16-channel planes per stage
-    static constexpr int XPIX = (TY + 2) * 34;                  // halo pixels per plane
-    static constexpr int G_IPL = TY;                            // glds per G plane (one row each)
+    static_assert(K::NCI % K::CW == 0, "ci tiles split evenly between the CW waves");
+    static constexpr int CO_T = 32 * K::NCO, CI_T = 32 * K::NCI;
+    static constexpr int GPL = 2 * K::NCO, XPL = 2 * K::NCI;    // 16-channel planes per stage
+    static constexpr int XPIX = (K::TY + 2) * 34;               // halo pixels per plane
+    static constexpr int G_IPL = K::TY;                         // glds per G plane (one row each)
     static constexpr int X_IPL = (XPIX * 2 + 63) / 64;          // glds per X plane
     // plane strides = 128 (mod 256) bytes: the two 16-lane groups of a half-wave
     // read the same pixels of planes 2e and 2e+1 → disjoint bank halves.
@@ -116,10 +126,11 @@ struct WG {
     static constexpr int STAGE = G_BYTES + XPL * X_PLANE;
     static constexpr int G_INSTR = GPL * G_IPL, INSTR = G_INSTR + XPL * X_IPL;
     static constexpr int IPW = (INSTR + SW - 1) / SW;
-    static constexpr int RED = CW * (KW - 1) * TN * 64 * (TN * NCO * NCIW * 16 + NCO) * 4;  // cross-wave K reduction
-    static constexpr int LDS = NSTG * STAGE > RED ? NSTG * STAGE : RED;
+    // cross-wave K reduction
+    static constexpr int RED = K::CW * (K::KW - 1) * TN * 64 * (TN * K::NCO * NCIW * 16 + K::NCO) * 4;
+    static constexpr int LDS = K::NSTG * STAGE > RED ? K::NSTG * STAGE : RED;
     static_assert(LDS <= 163840, "LDS budget");
-    static_assert((2 * TY) % KW == 0, "K groups split evenly between the KW waves of a row");
+    static_assert((2 * K::TY) % K::KW == 0, "K groups split evenly between the KW waves of a row");
 };
 
 struct WgradArgs {
@@ -666,17 +677,6 @@ static void launch_reduce(const WgradArgs& a, hipStream_t s) {
                        a);
 }
 
-// Variants (isr_wgrad3x3_variant; tools/tune_wgrad.py).  TY = pixel rows per
-// stage: a longer stage gives each barrier more MFMAs and halves the X halo
-// overhead ((TY+2)/TY), at the price of LDS (2 blocks/CU need <= 80 KB).
-template <int TY, int KW = 1>
-struct Fam {
-    using C22 = WG<2, 2, TY, KW>;
-    using C12 = WG<1, 2, TY, KW>;
-    using C21 = WG<2, 1, TY, KW>;
-    using C11 = WG<1, 1, TY, KW>;
-};
-
 static int wgrad_splits(const isr_wgrad_desc* d, int tiles, int pairs, int target, int min_splits = 1) {
     if (d->splits > 0) return d->splits < tiles ? d->splits : tiles;
     int s = (target + pairs - 1) / pairs;
@@ -748,6 +748,47 @@ static int launch_wgrad(const isr_wgrad_desc* d, void* ws, size_t ws_bytes, hipS
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// Variants (isr_wgrad3x3_variant; tools/tune_wgrad.py).  TY = pixel rows per
+// stage: a longer stage gives each barrier more MFMAs and halves the X halo
+// overhead ((TY+2)/TY), at the price of LDS (2 blocks/CU need <= 80 KB).
+// Named configurations: each spells the knobs in which it differs from WGKnobs (or from the record
+// it derives from).  K_<co tiles><ci tiles>: the kernel-row forms, TY_-row stages, KW_ waves per
+// kernel row, read form AR_; K_11T: the stride-2 phase conv, taps {0,1}^2, 4 waves
+template <int TY_, int KW_ = 1, int AR_ = 0> struct K_11 : WGKnobs { static constexpr int TY = TY_, KW = KW_, AR = AR_; };
+template <int AR_> struct K_11T : K_11<8, 2, AR_> { static constexpr int TWN = 1; };
+// K_CW<co tiles><ci tiles>: the ci-split forms, CW = NCI waves each owning one ci tile (K_CW24T:
+// taps {0,1}^2)
+template <int TY_, int AR_ = 0>
+struct K_CW22 : WGKnobs { static constexpr int NCO = 2, NCI = 2, TY = TY_, CW = 2, AR = AR_; };
+template <int AR_> struct K_CW23 : WGKnobs { static constexpr int NCO = 2, NCI = 3, CW = 3, AR = AR_; };
+template <int AR_> struct K_CW24 : WGKnobs { static constexpr int NCO = 2, NCI = 4, CW = 4, AR = AR_; };
+template <int AR_> struct K_CW24T : K_CW24<AR_> { static constexpr int TWN = 1; };
+// the row sweep (WGKnobs::RS) on the 32x32 tile with 8-row stages, 2 waves per kernel column
+struct K_RS8 : WGKnobs { static constexpr int TY = 8, KW = 2, RS = 1; };
+#ifdef ISR_TUNING  // earlier tile forms and probes (wgrad_pick variants 1-15, the cfg table of group_pick)
+template <int TY_, int KW_> struct K_12 : WGKnobs { static constexpr int NCI = 2, TY = TY_, KW = KW_; };
+template <int TY_, int KW_> struct K_21 : WGKnobs { static constexpr int NCO = 2, TY = TY_, KW = KW_; };
+template <int TY_, int KW_> struct K_22 : WGKnobs { static constexpr int NCO = 2, NCI = 2, TY = TY_, KW = KW_; };
+template <int TY_, int KW_> struct K_11N3 : K_11<TY_, KW_> { static constexpr int NSTG = 3; };  // 3-stage ring
+template <int TY_> struct K_CW12 : WGKnobs { static constexpr int NCI = 2, TY = TY_, CW = 2; };
+struct K_CW13 : WGKnobs { static constexpr int NCI = 3, CW = 3; };
+struct K_CW14 : WGKnobs { static constexpr int NCI = 4, CW = 4; };
+struct K_CW15 : WGKnobs { static constexpr int NCI = 5, CW = 5; };
+struct K_RS16 : K_RS8 { static constexpr int TY = 16; };     // 16-row stages (1 block / CU)
+struct K_RS8N3 : K_RS8 { static constexpr int NSTG = 3; };   // 3 stages
+struct K_RS8D : K_RS8 { static constexpr int RS = 1 | 2; };  // DMA one piece per row
+struct K_RS8A : K_RS8 { static constexpr int RS = 1 | 4; };  // 2 rows read ahead
+struct K_RS8DA : K_RS8 { static constexpr int RS = 1 | 2 | 4; };  // both
+struct K_RS8L : K_RS8 { static constexpr int RS = 1 | 8; };       // 2 loader waves
+struct K_RS8LA : K_RS8 { static constexpr int RS = 1 | 8 | 4; };  // + 2 rows read ahead
+template <int TY, int KW = 1>
+struct Fam {
+    using C22 = WG<K_22<TY, KW>>;
+    using C12 = WG<K_12<TY, KW>>;
+    using C21 = WG<K_21<TY, KW>>;
+    using C11 = WG<K_11<TY, KW>>;
+};
+
 template <class Fm, class F>
 static auto pick_in(const isr_wgrad_desc* d, bool co1, F&& f) {
     const bool co2 = !co1 && d->cout % 64 == 0, ci2 = d->cin % 64 == 0;
@@ -765,21 +806,23 @@ static auto pick_cw(const isr_wgrad_desc* d, F&& f, bool* ok) {
     if (d->taps == 0 && !d->x_sub2) {
         if (d->cout % 64 != 0) {  // cout 32 (growth convs)
             switch (d->cin) {
-                case 64: return f(WG<1, 2, TY, 1, 0, 2>());
-                case 96: return f(WG<1, 3, 4, 1, 0, 3>());
-                case 128: return f(WG<1, 4, 4, 1, 0, 4>());
-                case 160: return f(WG<1, 5, 4, 1, 0, 5>());
+                case 64: return f(WG<K_CW12<TY>>());
+                case 96: return f(WG<K_CW13>());
+                case 128: return f(WG<K_CW14>());
+                case 160: return f(WG<K_CW15>());
                 default: break;
             }
         } else if (d->cin == 192) {
-            return f(WG<2, 3, 4, 1, 0, 3>());
+            return f(WG<K_CW23<0>>());
         } else if (d->cin % 64 == 0) {
-            return f(WG<2, 2, TY, 1, 0, 2>());
+            return f(WG<K_CW22<TY>>());
         }
     }
     *ok = false;
     return f(Fam<4>::C11());
 }
+
+#endif
 
 // AR = 1 (production): the asm-read forms (WG::AR / WG::RS); 0 = compiler-visible LDS reads;
 // the 64 x 96 final-conv tile reads without read-ahead (AR 2: 8 B of scratch with it)
@@ -788,11 +831,11 @@ static auto pick_default(const isr_wgrad_desc* d, F&& f) {
     // the discriminator's wide layers (variant 14: -0.5 % per SRGAN step, same-box A/B): 64 co x
     // 128 (or 64) ci per block, 8-12 waves splitting the ci tiles, each pixel tile staged once
     if (d->cout % 64 == 0 && d->ha % 4 == 0 && !d->g_sub2) {
-        if (d->taps == 1 && d->cin % 128 == 0) return f(WG<2, 4, 4, 1, 1, 4, 2, 0, AR>());
-        if (d->taps == 0 && d->cout >= 128 && d->cin % 128 == 0) return f(WG<2, 4, 4, 1, 0, 4, 2, 0, AR>());
-        if (d->taps == 0 && d->cout >= 128 && d->cin % 64 == 0) return f(WG<2, 2, 4, 1, 0, 2, 2, 0, AR>());
+        if (d->taps == 1 && d->cin % 128 == 0) return f(WG<K_CW24T<AR>>());
+        if (d->taps == 0 && d->cout >= 128 && d->cin % 128 == 0) return f(WG<K_CW24<AR>>());
+        if (d->taps == 0 && d->cout >= 128 && d->cin % 64 == 0) return f(WG<K_CW22<4, AR>>());
     }
-    if (d->taps == 1) return f(WG<1, 1, 8, 2, 1, 1, 2, 0, AR>());  // stride-2 phase conv: taps {0,1}^2, 4 waves
+    if (d->taps == 1) return f(WG<K_11T<AR>>());  // stride-2 phase conv: taps {0,1}^2, 4 waves
     // production (tools/tune_wgrad.py, MI355X, N=16 128²): 32x32 (co, ci) tiles; 4-row
     // stages when cin % 64 == 32 (96, 160), else 8-row stages with 2 waves per kernel
     // row (variant 5): 4-11 % under the round-1 choice (16-row stages, 4 waves per
@@ -800,12 +843,12 @@ static auto pick_default(const isr_wgrad_desc* d, F&& f) {
     // the RDB final conv (cin 192, cout 64): 64x96 (co, ci) per block, 9 waves splitting the
     // ci tiles (each pixel tile staged once per block): 81-86 vs 98-104 us
     if (d->cin == 192 && d->cout == 64 && !d->g_sub2 && !d->x_sub2 && d->ha % 4 == 0)
-        return f(WG<2, 3, 4, 1, 0, 3, 2, 0, AR ? 2 : 0>());
-    if (d->cin % 64 == 32) return f(WG<1, 1, 4, 1, 0, 1, 2, 0, AR>());
+        return f(WG<K_CW23<AR ? 2 : 0>>());
+    if (d->cin % 64 == 32) return f(WG<K_11<4, 1, AR>>());
     // 8-row stages, 2 waves per kernel row; with AR as the row sweep (WG::RS, same bits)
-    if (d->ha % 8 == 0) return f(WG<1, 1, 8, 2, 0, 1, 2, AR, 0>());
-    if (d->ha % 4 == 0) return f(WG<1, 1, 4, 1, 0, 1, 2, 0, AR>());
-    return f(WG<1, 1, 2, 1, 0, 1, 2, 0, AR>());
+    if (d->ha % 8 == 0) return f(std::conditional_t<AR != 0, WG<K_RS8>, WG<K_11<8, 2>>>());
+    if (d->ha % 4 == 0) return f(WG<K_11<4, 1, AR>>());
+    return f(WG<K_11<2, 1, AR>>());
 }
 
 // variant 0: the production pick; 16: the same tiles and split counts with compiler-visible LDS
@@ -818,9 +861,9 @@ static auto wgrad_pick(const isr_wgrad_desc* d, int variant, F&& f) {
     switch (variant) {
         case 14: {  // ci-split forms for the discriminator's wide layers (64 co x 128 ci per block)
             if (d->cout % 64 == 0 && d->ha % 4 == 0) {
-                if (d->taps == 1 && d->cin % 128 == 0) return f(WG<2, 4, 4, 1, 1, 4>());
-                if (d->taps == 0 && d->cin % 128 == 0 && !d->g_sub2) return f(WG<2, 4, 4, 1, 0, 4>());
-                if (d->taps == 0 && d->cin % 64 == 0 && !d->g_sub2) return f(WG<2, 2, 4, 1, 0, 2>());
+                if (d->taps == 1 && d->cin % 128 == 0) return f(WG<K_CW24T<0>>());
+                if (d->taps == 0 && d->cin % 128 == 0 && !d->g_sub2) return f(WG<K_CW24<0>>());
+                if (d->taps == 0 && d->cin % 64 == 0 && !d->g_sub2) return f(WG<K_CW22<4>>());
             }
             break;
         }
@@ -843,7 +886,7 @@ static auto wgrad_pick(const isr_wgrad_desc* d, int variant, F&& f) {
         case 10: return f(Fam<4, 4>::C11());          // 4-row stages, 4 waves per kernel row
         case 11: return f(Fam<16, 2>::C11());         // 16-row stages, 2 waves per kernel row
         case 15:                                      // variant 5 as a row sweep (WG::RS)
-            if (d->taps == 0 && d->ha % 8 == 0) return f(WG<1, 1, 8, 2, 0, 1, 2, 1>());
+            if (d->taps == 0 && d->ha % 8 == 0) return f(WG<K_RS8>());
             break;
         default: break;
     }
@@ -943,24 +986,24 @@ static auto group_pick(const isr_wgrad_desc* ds, int n, F&& f, int variant = 0) 
     if (cfg == 2 && ty8) return f(Fam<8, 4>::C11());
     if (cfg == 3 && ty16) return f(Fam<16, 2>::C11());
     if (cfg == 4 && ty8) return f(Fam<8>::C11());
-    if (cfg == 5) return f(WG<1, 1, 4, 1, 0, 1, 3>());          // 4-row stages, 3-stage ring
-    if (cfg == 6) return f(WG<1, 1, 4, 2, 0, 1, 3>());          // 4-row stages, 2 waves per row, 3 stages
-    if (cfg == 7 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 3>());   // production tile, 3 stages (1 block / CU)
-    if (cfg == 8 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 2, 1>());   // production tile, row sweep
-    if (cfg == 9 && ty16) return f(WG<1, 1, 16, 2, 0, 1, 2, 1>()); // 16-row stages, row sweep (1 block / CU)
-    if (cfg == 10 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 3, 1>());  // row sweep, 3 stages
-    if (cfg == 11 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 2, 0, 1>());  // kernel-row form, asm reads
+    if (cfg == 5) return f(WG<K_11N3<4, 1>>());          // 4-row stages, 3-stage ring
+    if (cfg == 6) return f(WG<K_11N3<4, 2>>());          // 4-row stages, 2 waves per row, 3 stages
+    if (cfg == 7 && ty8) return f(WG<K_11N3<8, 2>>());   // production tile, 3 stages (1 block / CU)
+    if (cfg == 8 && ty8) return f(WG<K_RS8>());          // production tile, row sweep
+    if (cfg == 9 && ty16) return f(WG<K_RS16>());        // 16-row stages, row sweep (1 block / CU)
+    if (cfg == 10 && ty8) return f(WG<K_RS8N3>());       // row sweep, 3 stages
+    if (cfg == 11 && ty8) return f(WG<K_11<8, 2, 1>>());  // kernel-row form, asm reads
     if (cfg == 12) return ty8 ? f(Fam<8, 2>::C11()) : f(Fam<4>::C11());  // round-4 production
-    if (cfg == 13 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 2, 3>());  // row sweep + DMA one piece per row
-    if (cfg == 14 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 2, 5>());  // row sweep, 2 rows read ahead
-    if (cfg == 15 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 2, 7>());  // both
-    if (cfg == 16 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 2, 9>());  // row sweep + 2 loader waves
-    if (cfg == 17 && ty8) return f(WG<1, 1, 8, 2, 0, 1, 2, 13>()); // + 2 rows read ahead
+    if (cfg == 13 && ty8) return f(WG<K_RS8D>());   // row sweep + DMA one piece per row
+    if (cfg == 14 && ty8) return f(WG<K_RS8A>());   // row sweep, 2 rows read ahead
+    if (cfg == 15 && ty8) return f(WG<K_RS8DA>());  // both
+    if (cfg == 16 && ty8) return f(WG<K_RS8L>());   // row sweep + 2 loader waves
+    if (cfg == 17 && ty8) return f(WG<K_RS8LA>());  // + 2 rows read ahead
 #endif
     (void)ty16;
-    if (variant == 1) return ty8 ? f(WG<1, 1, 8, 2, 0, 1, 2, 0, 0>()) : f(WG<1, 1, 4, 1, 0, 1, 2, 0, 0>());
+    if (variant == 1) return ty8 ? f(WG<K_11<8, 2>>()) : f(WG<K_11<4>>());
     // 8-row stages, 2 waves per kernel column: the row sweep (WG::RS)
-    return ty8 ? f(WG<1, 1, 8, 2, 0, 1, 2, 1>()) : f(WG<1, 1, 4, 1, 0, 1, 2, 0, 1>());
+    return ty8 ? f(WG<K_RS8>()) : f(WG<K_11<4, 1, 1>>());
 }
 
 size_t wgrad3x3_group_workspace_bytes(const isr_wgrad_desc* ds, int n, int variant) {
