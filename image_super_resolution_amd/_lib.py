@@ -78,7 +78,7 @@ class IsrSrTransformDesc(ctypes.Structure):
 class IsrConvertDesc(ctypes.Structure):
     _fields_ = [("n", c_int32), ("h", c_int32), ("w", c_int32), ("ha", c_int32), ("wa", c_int32), ("c", c_int32),
                 ("nchw", c_void_p), ("v", IsrView), ("scale", c_void_p), ("shift", c_void_p),
-                ("m", IsrView), ("mslope", c_float), ("f16", c_int32)]
+                ("m", IsrView), ("mslope", c_float)]
 
 
 class IsrPoolDesc(ctypes.Structure):

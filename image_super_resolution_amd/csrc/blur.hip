@@ -20,6 +20,7 @@
 // 0..7 of rows r, r + 4, r + 8, r + 12, whose first dwords are 40, 80, 120 dwords = 8, 16, 24
 // banks apart (ds_read_b32 banks are dword mod 32), so the three reads per row are conflict-free.
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(256) void blur_u8_kernel(isr_blur_desc d, int tiles
 int blur_u8_dispatch(const isr_blur_desc* d, hipStream_t s) {
     const int tiles_x = (d->w + BL_TW - 1) / BL_TW, tiles_y = (d->h + BL_TH - 1) / BL_TH;
     const long long blocks = (long long)d->n * tiles_x * tiles_y;
-    if (blocks >= (1ll << 31)) return -2;
+    if (blocks >= (1ll << 31)) return DISPATCH_UNSUPPORTED;
     const int vec_out = (d->w & 3) == 0 && ((uintptr_t)d->dst & 3) == 0;
     hipLaunchKernelGGL(blur_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *d, tiles_x, tiles_y, vec_out);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -628,12 +629,12 @@ static int launch3x3_k(const isr_conv_desc* d, hipStream_t s) {
 // take the plain form only (x_sub2 → unsupported).
 template <class C, bool FULL = false>
 static int launch3x3(const isr_conv_desc* d, hipStream_t s) {
-    if (d->cout % C::CT || d->cin % C::KC || d->ha % C::TH) return -2;
-    if (C::CIN && d->cin != C::CIN) return -2;
+    if (d->cout % C::CT || d->cin % C::KC || d->ha % C::TH) return DISPATCH_UNSUPPORTED;
+    if (C::CIN && d->cin != C::CIN) return DISPATCH_UNSUPPORTED;
     if constexpr (FULL) {
         if (d->x_sub2) return launch3x3_k<C, true>(d, s);
     } else {
-        if (d->x_sub2) return -2;
+        if (d->x_sub2) return DISPATCH_UNSUPPORTED;
     }
     return launch3x3_k<C, false>(d, s);
 }
@@ -700,7 +701,7 @@ static bool fold_host(const isr_conv_desc* d) {
 
 int conv3x3_fwd_variant(const isr_conv_desc* d, int variant, hipStream_t s) {
     if (d->f16) {  // fp16 storage: the production tiles only (the inference forward)
-        if (variant != 0 || d->x_sub2 || d->taps || d->m.data) return -2;
+        if (variant != 0 || d->x_sub2 || d->taps || d->m.data) return DISPATCH_UNSUPPORTED;
         if (d->cout % 64) return launch3x3<V_G0H>(d, s);
         return d->cin == 192 ? (fold_host(d) ? launch3x3<V_F0FH>(d, s) : launch3x3<V_F0H>(d, s)) : launch3x3<V_W0H>(d, s);
     }
@@ -721,7 +722,7 @@ int conv3x3_fwd_variant(const isr_conv_desc* d, int variant, hipStream_t s) {
             case 7: return launch3x3<C3<K_GAbl<3>>>(d, s);
 #endif
         }
-        return -2;
+        return DISPATCH_UNSUPPORTED;
     }
     switch (variant) {
         case 0: return d->cin == 192 ? (fold_host(d) ? launch3x3<V_F0F>(d, s) : launch3x3<V_F0, true>(d, s))
@@ -742,19 +743,19 @@ int conv3x3_fwd_variant(const isr_conv_desc* d, int variant, hipStream_t s) {
         case 7: return launch3x3<C3<K_WAbl<3>>>(d, s);
 #endif
     }
-    return -2;
+    return DISPATCH_UNSUPPORTED;
 }
 
 #ifdef ISR_TUNING
 int conv_stamps_set(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_conv_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -1; }
 #else
-int conv_stamps_set(void*) { return -2; }
+int conv_stamps_set(void*) { return DISPATCH_UNSUPPORTED; }
 #endif
 
 int conv3x3_fwd_dispatch(const isr_conv_desc* d, hipStream_t s) {
     if (d->f16) return conv3x3_fwd_variant(d, 0, s);
-    if (d->taps == 1) return d->cout % 64 ? -2 : launch3x3<C3<K_T01>, true>(d, s);
-    if (d->taps == 2) return d->cout % 64 ? -2 : launch3x3<C3<K_T12>, true>(d, s);
+    if (d->taps == 1) return d->cout % 64 ? DISPATCH_UNSUPPORTED : launch3x3<C3<K_T01>, true>(d, s);
+    if (d->taps == 2) return d->cout % 64 ? DISPATCH_UNSUPPORTED : launch3x3<C3<K_T12>, true>(d, s);
     return conv3x3_fwd_variant(d, 0, s);
 }
 

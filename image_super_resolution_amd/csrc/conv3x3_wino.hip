@@ -29,6 +29,7 @@
 // read from column x = wa instead (the border; they feed only outputs that are not stored) and
 // no residual load or store is formed at x >= wa.
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 

@@ -14,6 +14,7 @@
 //       the tile; stage 2 sums out[y][x][co] = sum_ky T[y+ky-4][x][(ky,co)] in
 //       LDS and applies bias + tanh (+ uint8 quantisation).
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -547,7 +548,7 @@ int tail_segment_rows(const isr_tail_desc* d, int cus) {
 // whose output passes 2 GiB.  -2: any other id.
 int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s) {
     if (variant == 0) variant = 5;
-    if (variant != 3 && variant != 5) return -2;
+    if (variant != 3 && variant != 5) return DISPATCH_UNSUPPORTED;
     const int sh = variant == 5 ? tail_segment_rows(d, cu_count()) : 0;
     if (sh == 0) variant = 3;
     if (variant == 3) {
@@ -558,7 +559,7 @@ int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s) {
         };
         return d->f16 ? go(tail9x9_k8_kernel<true>) : go(tail9x9_k8_kernel<false>);
     }
-    if (sh < 8) return -2;
+    if (sh < 8) return DISPATCH_UNSUPPORTED;
     const int blocks = d->n * (d->wa / tail8w::TW) * (d->ha / sh);
     auto go = [&](auto kern) {
         lds_limit((const void*)kern, tail8w::LDS);
@@ -569,7 +570,7 @@ int tail9x9_fwd_variant(const isr_tail_desc* d, int variant, hipStream_t s) {
 }
 
 // no shipping tail kernel writes stamps (only the removed 4-wave walk did)
-int tail_stamps_set(void*) { return -2; }
+int tail_stamps_set(void*) { return DISPATCH_UNSUPPORTED; }
 
 int tail9x9_fwd_dispatch(const isr_tail_desc* d, hipStream_t s) { return tail9x9_fwd_variant(d, 0, s); }
 

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -447,7 +448,7 @@ size_t jpeg_roundtrip_workspace_bytes(const isr_jpeg_desc* d) {
 }
 
 int jpeg_roundtrip_dispatch(const isr_jpeg_desc* d, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < jpeg_roundtrip_workspace_bytes(d)) return -3;
+    if (ws_bytes < jpeg_roundtrip_workspace_bytes(d)) return DISPATCH_WS_TOO_SMALL;
     JpegArgs p;
     p.src = d->src;
     p.dst = d->dst;

@@ -22,6 +22,7 @@
 // members' source tiles go to LDS first (4 x 32 x 33 floats = 16.5 KB); element e of quad q reads row
 // 4 q + e, column = its output row: a half holds 8 quads x 4 rows, banks 4 q + row: conflict-free.
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -259,7 +260,7 @@ int dihedral_dispatch(const isr_dihedral_desc* d, hipStream_t s) {
     int tiles_y, tiles_x;
     const long long blocks = tile_blocks((long long)d->n * d->c, t ? d->w : d->h, t ? d->h : d->w,
                                          d->elem == 1 ? D8_T : D32_T, tiles_y, tiles_x);
-    if (blocks >= (1ll << 31)) return -2;
+    if (blocks >= (1ll << 31)) return DISPATCH_UNSUPPORTED;
     if (d->elem == 1)
         hipLaunchKernelGGL(dihedral_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, *d, tiles_x, tiles_y);
     else
@@ -270,7 +271,7 @@ int dihedral_dispatch(const isr_dihedral_desc* d, hipStream_t s) {
 int ensemble_expand_u8_dispatch(const isr_ensemble_expand_desc* d, hipStream_t s) {
     int tiles_h, tiles_w;
     const long long blocks = tile_blocks(8ll * d->n * 3, d->h, d->w, D8_T, tiles_h, tiles_w);
-    if (blocks >= (1ll << 31)) return -2;
+    if (blocks >= (1ll << 31)) return DISPATCH_UNSUPPORTED;
     hipLaunchKernelGGL(ensemble_expand_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *d, tiles_h, tiles_w);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -278,7 +279,7 @@ int ensemble_expand_u8_dispatch(const isr_ensemble_expand_desc* d, hipStream_t s
 int ensemble_reduce_dispatch(const isr_ensemble_reduce_desc* d, hipStream_t s) {
     int tiles_y, tiles_x;
     const long long blocks = tile_blocks((long long)d->n * 3, d->h, d->w, D32_T, tiles_y, tiles_x);
-    if (blocks >= (1ll << 31)) return -2;
+    if (blocks >= (1ll << 31)) return DISPATCH_UNSUPPORTED;
     hipLaunchKernelGGL(ensemble_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *d, tiles_x, tiles_y);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

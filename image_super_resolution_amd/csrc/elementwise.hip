@@ -2,6 +2,7 @@
 // One thread per (pixel, 8 channels): 16-byte loads/stores, whole computed
 // region (ha x wa), zeros written outside the valid h x w region.
 #include "isr_common.h"
+#include "dispatch.h"
 
 // Index type of the grid-stride elementwise kernels: 32-bit (cheap div/mod for the
 // pixel decomposition) whenever the element-group count leaves headroom for the stride.
@@ -499,7 +500,7 @@ int bn_dispatch(const isr_bn_desc* d, int op, hipStream_t s) {
         case 2: ISR_IDX_LAUNCH(bn_apply_kernel, total, dim3(ew_blocks), s, *d); break;
         case 3: hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3(red_blocks), dim3(256), 0, s, *d); break;
         case 4: ISR_IDX_LAUNCH(bn_bwd_apply_kernel, total, dim3(ew_blocks), s, *d); break;
-        default: return -2;
+        default: return DISPATCH_UNSUPPORTED;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -557,7 +558,7 @@ int sr_transform_dispatch(const isr_sr_transform_desc* d, hipStream_t s) {
         case 2: hipLaunchKernelGGL(sr_transform_kernel<2>, dim3(blocks), dim3(256), 0, s, *d); break;
         case 3: hipLaunchKernelGGL(sr_transform_kernel<3>, dim3(blocks), dim3(256), 0, s, *d); break;
         case 4: hipLaunchKernelGGL(sr_transform_kernel<4>, dim3(blocks), dim3(256), 0, s, *d); break;
-        default: return -2;
+        default: return DISPATCH_UNSUPPORTED;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

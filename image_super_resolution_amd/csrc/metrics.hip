@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -237,7 +238,7 @@ size_t image_metrics_workspace_bytes(const isr_metrics_desc* d) {
 }
 
 int image_metrics_dispatch(const isr_metrics_desc* d, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < image_metrics_workspace_bytes(d)) return -3;
+    if (ws_bytes < image_metrics_workspace_bytes(d)) return DISPATCH_WS_TOO_SMALL;
     MetricsArgs p;
     p.a = d->a;
     p.b = d->b;

@@ -6,6 +6,7 @@
 // Work is a list of chunks (tensor index, start, length) built by the host; a
 // block owns one chunk and streams it with 16-byte accesses (HBM-bound).
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 

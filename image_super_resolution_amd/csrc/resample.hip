@@ -17,6 +17,7 @@
 // coefficient rows at an odd dword stride: 28.7 KB static, five blocks per CU.  The row bound 176
 // covers the worst supported case, lanczos at ratio 8: 15 * 8 + 2 * 24 + 2 = 170 rows.
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(isr_resample_desc d, i
 int resample_u8_dispatch(const isr_resample_desc* d, hipStream_t s) {
     const int tiles_x = (d->out_w + RS_TW - 1) / RS_TW, tiles_y = (d->out_h + RS_TH - 1) / RS_TH;
     const long long blocks = (long long)d->n * tiles_x * tiles_y;
-    if (blocks >= (1ll << 31)) return -2;
+    if (blocks >= (1ll << 31)) return DISPATCH_UNSUPPORTED;
     hipLaunchKernelGGL(resample_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *d, tiles_x, tiles_y);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

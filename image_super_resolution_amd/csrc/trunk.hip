@@ -26,6 +26,7 @@
 // consumers poll the 9 neighbour words (sc1 loads, per wave) and read activations with sc1
 // LDS-DMA.  Progress words are serial numbers gen * 1024 + layers done (no zeroing per call).
 #include "trunk_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -1306,10 +1307,10 @@ __global__ __launch_bounds__(TK::NT, TK::WPS) void trunk_kernel(TrunkArgs a) {
 // what the build is made for); ISR_ERR when that is below one workgroup per CU.
 template <bool H>
 static int trunk_launch_k(const isr_chain_desc* cd, hipStream_t s) {
-    if (cd->ha % TK::TH || cd->wa % tk::TW || cd->nl < 1 || cd->nl > 1024) return -2;
+    if (cd->ha % TK::TH || cd->wa % tk::TW || cd->nl < 1 || cd->nl > 1024) return DISPATCH_UNSUPPORTED;
     const int nbx = cd->wa / tk::TW, nby = cd->ha / TK::TH;
     const long long ntiles = (long long)cd->n * nbx * nby;
-    if (ntiles <= 0 || ntiles > (1 << 24)) return -2;
+    if (ntiles <= 0 || ntiles > (1 << 24)) return DISPATCH_UNSUPPORTED;
     static thread_local int cached_dev = -1, cached_per_cu = 0, cached_cus = 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
@@ -1328,7 +1329,7 @@ static int trunk_launch_k(const isr_chain_desc* cd, hipStream_t s) {
 #ifdef ISR_TUNING
     if (g_trunk_per_cu > 0 && g_trunk_per_cu < per_cu) per_cu = g_trunk_per_cu;
 #endif
-    if (per_cu < 1) return -4;
+    if (per_cu < 1) return DISPATCH_NO_OCCUPANCY;
     const long long slots = (long long)per_cu * cached_cus;
     const int grid = (int)(ntiles < slots ? ntiles : slots);
     const int rec_off = (int)trunk_rec_off((int)ntiles);
@@ -1365,9 +1366,9 @@ int trunk_item_stamps_set(void* p) {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_item_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -1;
 }
 #else
-int trunk_knobs_set(const int*) { return -2; }
-int trunk_stamps_set(void*) { return -2; }
-int trunk_item_stamps_set(void*) { return -2; }
+int trunk_knobs_set(const int*) { return DISPATCH_UNSUPPORTED; }
+int trunk_stamps_set(void*) { return DISPATCH_UNSUPPORTED; }
+int trunk_item_stamps_set(void*) { return DISPATCH_UNSUPPORTED; }
 #endif
 
 }  // namespace isr

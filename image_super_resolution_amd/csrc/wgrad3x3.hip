@@ -23,6 +23,7 @@
 // reduces over splits, applies `scale`, and writes dW in the reference OIHW
 // layout (and un-permutes the PixelShuffle channel order for g_sub2).
 #include "isr_common.h"
+#include "dispatch.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -705,11 +706,11 @@ static void wgrad_geometry(const isr_wgrad_desc* d, int* tiles, int* splits) {
 // parts: 1 = the split-K partials, 2 = their reduction into dW / db, 3 = both (in stream order)
 template <class C>
 static int launch_wgrad(const isr_wgrad_desc* d, void* ws, size_t ws_bytes, hipStream_t s, int parts = 3) {
-    if (d->ha % C::TY || d->cout % C::CO_T || d->cin % C::CI_T) return -2;
+    if (d->ha % C::TY || d->cout % C::CO_T || d->cin % C::CI_T) return DISPATCH_UNSUPPORTED;
     WgradArgs a;
     a.d = *d;
     wgrad_geometry<C>(d, &a.tiles, &a.splits);
-    if (ws_bytes < ((size_t)a.splits * 9 * d->cout * d->cin + (size_t)a.splits * d->cout) * 4) return -3;
+    if (ws_bytes < ((size_t)a.splits * 9 * d->cout * d->cin + (size_t)a.splits * d->cout) * 4) return DISPATCH_WS_TOO_SMALL;
     a.ws = (float*)ws;
 #ifdef ISR_TUNING
     // timing probes of the training step (outputs wrong): no weight gradients at all / no reduce
@@ -915,13 +916,13 @@ int wgrad3x3_dispatch(const isr_wgrad_desc* d, int variant, void* ws, size_t ws_
 // wa; 32x32 (co, ci) tiles, 8-row stages with 2 waves per kernel row (4-row stages when ha % 8)
 template <class C>
 static int group_plan(const isr_wgrad_desc* ds, int n, WgradGroupArgs* g, size_t* bytes) {
-    if (n < 1 || n > WG_GROUP_MAX) return -2;
+    if (n < 1 || n > WG_GROUP_MAX) return DISPATCH_UNSUPPORTED;
     int pairs = 0;
     for (int t = 0; t < n; ++t) {
         const isr_wgrad_desc& d = ds[t];
         if (d.g_sub2 || d.x_sub2 || d.taps || d.cout % C::CO_T || d.cin % C::CI_T || d.ha % C::TY || d.n != ds[0].n ||
             d.ha != ds[0].ha || d.wa != ds[0].wa)
-            return -2;
+            return DISPATCH_UNSUPPORTED;
         pairs += (d.cout / C::CO_T) * (d.cin / C::CI_T);
     }
     const int tiles = ds[0].n * (ds[0].ha / C::TY) * (ds[0].wa / 32);
@@ -1021,7 +1022,7 @@ int wgrad3x3_group_dispatch(const isr_wgrad_desc* ds, int n, void* ws, size_t ws
         size_t bytes = 0;
         const int rc = group_plan<C>(ds, n, &g, &bytes);
         if (rc) return rc;
-        if (ws_bytes < bytes) return -3;
+        if (ws_bytes < bytes) return DISPATCH_WS_TOO_SMALL;
         for (int t = 0; t < n; ++t) g.ws[t] = (float*)((char*)ws + (uintptr_t)g.ws[t]);
         auto kern = wgrad3x3_group_kernel<C>;
         lds_limit((const void*)kern, C::LDS);

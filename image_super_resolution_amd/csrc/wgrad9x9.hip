@@ -17,6 +17,7 @@
 // is staged with global_load_lds and read with ds_read_b64_tr_b16 (as in
 // wgrad3x3.hip).  Split-K partials + reduce as in wgrad3x3.hip.
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 
@@ -243,7 +244,7 @@ static int launch_w9(const isr_wgrad9_desc* d, void* ws, size_t ws_bytes, hipStr
     W9Args a;
     a.d = *d;
     w9_geometry<C>(d, &a.tiles, &a.splits);
-    if (ws_bytes < (size_t)a.splits * (9 * 32 * 64 + 64) * 4) return -3;
+    if (ws_bytes < (size_t)a.splits * (9 * 32 * 64 + 64) * 4) return DISPATCH_WS_TOO_SMALL;
     a.ws = (float*)ws;
     auto kern = wgrad9x9_kernel<C>;
     lds_limit((const void*)kern, C::LDS);

@@ -17,6 +17,7 @@
 // from h, w and the thread's position, chroma neighbours are clamped to the plane: nothing a caller
 // puts into the coefficients can move an access.
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 

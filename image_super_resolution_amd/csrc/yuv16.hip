@@ -19,6 +19,7 @@
 // h, w and the thread's position, chroma neighbours are clamped to the plane and every sample is masked
 // to its 10 bits: nothing a caller puts into the words or the coefficients can move an access.
 #include "isr_common.h"
+#include "dispatch.h"
 
 namespace isr {
 

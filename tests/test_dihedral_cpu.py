@@ -1,17 +1,11 @@
 """The dihedral transforms without a GPU: the group itself (tests/dihedral_ref.py against
-isr_dihedral_inverse), one refusal table for isr_dihedral, isr_ensemble_expand_u8 and isr_ensemble_reduce in
-the style of tests/test_capi_refusals.py (every call is refused before anything is launched or dereferenced,
-so the pointers are made-up aligned addresses), and the command-line and constructor ends of both features."""
-import ctypes
-
+isr_dihedral_inverse) and the command-line and constructor ends of both features.  What isr_dihedral,
+isr_ensemble_expand_u8 and isr_ensemble_reduce refuse is in tests/test_capi_refusals.py."""
 import pytest
 import torch
 
 import dihedral_ref as ref
 from image_super_resolution_amd import _lib
-
-BAD_DESC, UNSUPPORTED = -1, -2
-P = 0x10000  # aligned, never followed
 
 
 def test_the_eight_ops_are_different_and_each_has_its_inverse():
@@ -41,73 +35,6 @@ def test_inverse_entry_point(built_lib):
     assert [dihedral.inverse(k) for k in range(8)] == [0, 3, 2, 1, 4, 5, 6, 7]
     with pytest.raises(ValueError):
         dihedral.inverse(8)
-
-
-# entry point -> (descriptor class, a descriptor that passes every check)
-ENTRIES = {
-    "dihedral": (_lib.IsrDihedralDesc, dict(n=2, c=3, h=16, w=24, elem=1, op=1, ops=None, x=P, y=2 * P)),
-    "ensemble_expand_u8": (_lib.IsrEnsembleExpandDesc, dict(n=2, h=16, w=24, x=P, even=2 * P, odd=3 * P)),
-    "ensemble_reduce": (_lib.IsrEnsembleReduceDesc, dict(n=2, h=16, w=24, even=P, odd=2 * P, y=3 * P, y_u8=1)),
-}
-
-# (entry point, descriptor fields to change (None: a null descriptor), return code, further substrings of the message)
-TABLE = [
-    ("dihedral", None, BAD_DESC, ("null descriptor",)),
-    ("dihedral", dict(x=None), BAD_DESC, ("null",)),
-    ("dihedral", dict(y=None), BAD_DESC, ("null",)),
-    ("dihedral", dict(elem=4, x=P + 2), BAD_DESC, ("aligned",)),
-    ("dihedral", dict(elem=4, y=2 * P + 1), BAD_DESC, ("aligned",)),
-    ("dihedral", dict(h=16, w=16, ops=3 * P + 2), BAD_DESC, ("aligned",)),
-    ("dihedral", dict(y=P), BAD_DESC, ("must not be x",)),
-    ("dihedral", dict(n=0), BAD_DESC, ("n=0",)),
-    ("dihedral", dict(n=-1), BAD_DESC, ()),
-    ("dihedral", dict(n=65536), BAD_DESC, ()),
-    ("dihedral", dict(c=0), BAD_DESC, ("c=0",)),
-    ("dihedral", dict(c=65536), BAD_DESC, ()),
-    ("dihedral", dict(h=0), BAD_DESC, ("smaller than",)),
-    ("dihedral", dict(w=-3), BAD_DESC, ("smaller than",)),
-    ("dihedral", dict(h=1 << 16, w=1 << 15), UNSUPPORTED, ("31 bits",)),
-    ("dihedral", dict(elem=2), UNSUPPORTED, ("elem 2",)),
-    ("dihedral", dict(elem=0), UNSUPPORTED, ("elem 0",)),
-    ("dihedral", dict(ops=3 * P), UNSUPPORTED, ("square",)),
-    ("dihedral", dict(op=8), UNSUPPORTED, ("op 8",)),
-    ("dihedral", dict(op=-1), UNSUPPORTED, ("op -1",)),
-    ("ensemble_expand_u8", None, BAD_DESC, ("null descriptor",)),
-    ("ensemble_expand_u8", dict(x=None), BAD_DESC, ("null",)),
-    ("ensemble_expand_u8", dict(even=None), BAD_DESC, ("null",)),
-    ("ensemble_expand_u8", dict(odd=None), BAD_DESC, ("null",)),
-    ("ensemble_expand_u8", dict(even=P), BAD_DESC, ("same buffer",)),
-    ("ensemble_expand_u8", dict(odd=2 * P), BAD_DESC, ("same buffer",)),
-    ("ensemble_expand_u8", dict(n=0), BAD_DESC, ()),
-    ("ensemble_expand_u8", dict(n=16384), BAD_DESC, ("16383",)),
-    ("ensemble_expand_u8", dict(w=0), BAD_DESC, ("smaller than",)),
-    ("ensemble_expand_u8", dict(h=1 << 16, w=1 << 15), UNSUPPORTED, ("31 bits",)),
-    ("ensemble_reduce", None, BAD_DESC, ("null descriptor",)),
-    ("ensemble_reduce", dict(even=None), BAD_DESC, ("null",)),
-    ("ensemble_reduce", dict(odd=None), BAD_DESC, ("null",)),
-    ("ensemble_reduce", dict(y=None), BAD_DESC, ("null",)),
-    ("ensemble_reduce", dict(y=P), BAD_DESC, ("same buffer",)),
-    ("ensemble_reduce", dict(odd=P), BAD_DESC, ("same buffer",)),
-    ("ensemble_reduce", dict(even=P + 2), BAD_DESC, ("aligned",)),
-    ("ensemble_reduce", dict(y_u8=0, y=3 * P + 1), BAD_DESC, ("aligned",)),
-    ("ensemble_reduce", dict(n=0), BAD_DESC, ()),
-    ("ensemble_reduce", dict(n=16384), BAD_DESC, ("16383",)),
-    ("ensemble_reduce", dict(h=0), BAD_DESC, ("smaller than",)),
-    ("ensemble_reduce", dict(h=1 << 16, w=1 << 15), UNSUPPORTED, ("31 bits",)),
-]
-
-
-def test_refused_without_a_launch(built_lib):
-    """Every row of the table; all rows that miss are reported together."""
-    missed = []
-    for entry, change, code, says in TABLE:
-        cls, good = ENTRIES[entry]
-        desc = None if change is None else ctypes.byref(cls(**{**good, **change}))
-        rc = getattr(built_lib, "isr_" + entry)(desc, None)
-        msg = built_lib.isr_last_error().decode()
-        if rc != code or not all(s in msg for s in (entry, *says)):
-            missed.append((entry, change, f"returned {rc}, expected {code}", msg, says))
-    assert not missed, "\n".join(map(str, missed))
 
 
 def test_python_entry_points_refuse_cpu_tensors():

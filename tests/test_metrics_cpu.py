@@ -1,5 +1,5 @@
 """The image metrics without a GPU: the fp64 restatement against the oracle, the C struct layout,
-descriptor refusals (nothing is launched), Evaluator.merge across a gloo world, train.py's flags."""
+Evaluator.merge across a gloo world, train.py's flags (the refusals: tests/test_capi_refusals.py)."""
 import ctypes
 import os
 import socket
@@ -76,32 +76,6 @@ def test_metrics_desc_layout_matches_c(tmp_path):
     assert set(c) == {f[0] for f in _lib.IsrMetricsDesc._fields_}
     for name, off in c.items():
         assert getattr(_lib.IsrMetricsDesc, name).offset == int(off), name
-
-
-def _desc(n, h, w, border, ptr=1 << 20):
-    f3 = ctypes.c_float * 3
-    return _lib.IsrMetricsDesc(n, h, w, border, ptr, ptr, 1, 1, f3(1, 1, 1), f3(), f3(1, 1, 1), f3(), 1, 0, ptr)
-
-
-def test_refusals_touch_no_gpu(built_lib):
-    """Dummy non-null pointers: a refused descriptor is never dereferenced or launched."""
-    lib = built_lib
-    assert lib.isr_image_metrics(None, None, 0, None) == -1
-    assert b"null descriptor" in lib.isr_last_error()
-    assert lib.isr_image_metrics_workspace_bytes(None) == 0
-    d = _desc(1, 64, 64, 4, ptr=None)
-    assert lib.isr_image_metrics(ctypes.byref(d), ctypes.c_void_p(1 << 20), 1 << 20, None) == -1
-    assert b"null" in lib.isr_last_error()
-    for bad in ((0, 64, 64), (1, 0, 64), (1, 64, -3)):
-        assert lib.isr_image_metrics(ctypes.byref(_desc(*bad, 4)), ctypes.c_void_p(1 << 20), 1 << 20, None) == -1
-    d = _desc(1, 20, 30, 5)  # hc = 10: one short of the window
-    assert lib.isr_image_metrics(ctypes.byref(d), ctypes.c_void_p(1 << 20), 1 << 20, None) == -2
-    assert b"11-pixel" in lib.isr_last_error() and b"window" in lib.isr_last_error()
-    assert lib.isr_image_metrics_workspace_bytes(ctypes.byref(d)) == 0
-    ok = _desc(2, 75, 43, 4)
-    assert lib.isr_image_metrics_workspace_bytes(ctypes.byref(ok)) > 0
-    assert lib.isr_image_metrics(ctypes.byref(ok), None, 0, None) == -1  # null workspace, still no launch
-    assert b"workspace" in lib.isr_last_error()
 
 
 # Per-image values that are small dyadic rationals: every partial sum is exact in fp64, so the

@@ -1,8 +1,7 @@
-"""The fp16 Winograd F(2,3) conv path, checks that need no GPU: the three C-ABI exports and their
-validation (nothing launched), the CPU restatement tests/wino_ref.py against the plain conv with
+"""The fp16 Winograd F(2,3) conv path, checks that need no GPU: the three C-ABI exports (what they
+refuse: tests/test_capi_refusals.py), the CPU restatement tests/wino_ref.py against the plain conv with
 its roundings switched off (pins the transform matrices independently of any kernel), and the
 engine's refusals of `wino` with bf16 storage or with the chained trunk."""
-import ctypes
 import re
 import subprocess
 import types
@@ -21,48 +20,6 @@ def test_wino_symbols_exported(built_lib):
     for name in ("isr_conv3x3_wino_packed_bytes", "isr_pack_conv3x3_wino_f16", "isr_conv3x3_wino_fwd"):
         assert name in exported and name in _lib.SIGNATURES, name
     assert built_lib.isr_conv3x3_wino_packed_bytes(64, 192) == 64 * 192 * 12 * 2
-
-
-def _desc():
-    """A descriptor the Winograd entry point's own field checks accept (views still null)."""
-    d = _lib.IsrConvDesc()
-    d.n, d.h, d.w, d.ha, d.wa, d.cin, d.cout = 1, 16, 32, 32, 32, 64, 64
-    d.shuffle, d.f16 = 1, 1
-    d.slope = d.s1 = d.s2 = 1.0
-    return d
-
-
-def test_wino_validation_rejects_without_touching_gpu(built_lib):
-    lib = built_lib
-    assert lib.isr_conv3x3_wino_fwd(None, None) == -1
-    assert b"null descriptor" in lib.isr_last_error()
-    for field, value in (("f16", 0), ("shuffle", 2), ("x_sub2", 1), ("taps", 1)):
-        d = _desc()
-        setattr(d, field, value)
-        assert lib.isr_conv3x3_wino_fwd(ctypes.byref(d), None) == -2, field
-        assert field.encode() in lib.isr_last_error(), (field, lib.isr_last_error())
-    d = _desc()
-    keep = torch.zeros(16)
-    d.m = _lib.IsrView(keep.data_ptr(), 34, 34, 64, 1, 0)  # a mask source: the backward form
-    assert lib.isr_conv3x3_wino_fwd(ctypes.byref(d), None) == -2
-    assert b"mask" in lib.isr_last_error()
-    # past its own checks the direct form's descriptor rules apply: null views / weights
-    assert lib.isr_conv3x3_wino_fwd(ctypes.byref(_desc()), None) == -1
-    d = _desc()
-    d.cin = 40
-    assert lib.isr_conv3x3_wino_fwd(ctypes.byref(d), None) == -2
-    assert b"multiple of 16" in lib.isr_last_error()
-
-
-def test_wino_pack_validation(built_lib):
-    lib = built_lib
-    assert lib.isr_pack_conv3x3_wino_f16(None, None, 64, 64, None) == -1
-    assert b"null pointer" in lib.isr_last_error()
-    keep = torch.zeros(16)
-    p = keep.data_ptr()  # never dereferenced: validation fails first
-    assert lib.isr_pack_conv3x3_wino_f16(p, p, 64, 40, None) == -2
-    assert b"cin 40" in lib.isr_last_error()
-    assert lib.isr_pack_conv3x3_wino_f16(p, p, 48, 64, None) == -2
 
 
 @pytest.mark.parametrize("n,cin,cout,h,w", [(1, 16, 32, 8, 6), (1, 192, 64, 18, 40), (2, 32, 32, 5, 7)])

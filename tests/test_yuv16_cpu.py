@@ -2,8 +2,8 @@
 (isr_yuv_coeffs_depth) against isr_yuv_coeffs and the numpy restatement (tests/yuv16_ref.py), the integer
 restatement against fp64 with bounds derived from the tables, the int32 overflow the GPU extremes test
 relies on, flat-colour round trips, the tanh quantiser against rational arithmetic, the 10-bit Y4M
-header, readers and recorder, YUVFormat at both depths, rs.py's flags, the ffmpeg argv, the
-descriptor's layout against C and every refusal of the two entry points."""
+header, readers and recorder, YUVFormat at both depths, rs.py's flags, the ffmpeg argv and the
+descriptor's layout against C (every refusal of the two entry points: tests/test_capi_refusals.py)."""
 import ctypes
 import itertools
 import subprocess
@@ -379,39 +379,3 @@ def test_desc_layout_matches_c(tmp_path):
     for name in names:
         assert getattr(_lib.IsrYuv16Desc, name).offset == int(c[name][0]), name
     assert [int(v) for v in c["consts"]] == [0, 1, 2] == [yuv.RGB_KINDS.index(k) for k in ("u16", "norm_f32", "tanh_f32")]
-
-
-def test_entry_point_refusals():
-    """Descriptor validation happens before any launch: no GPU is touched by a refused call."""
-    lib = _lib.load()
-    buf = np.zeros(8192, dtype=np.uint8)
-    base = buf.ctypes.data + (-buf.ctypes.data) % 16
-    src, dst = base, base + 4096
-    U16, NORM, TANH = 0, 1, 2
-
-    def desc(n=1, h=4, w=4, layout=0, siting=0, depth=10, shift=0, kind=U16, s=src, d=dst):
-        return _lib.IsrYuv16Desc(n, h, w, layout, siting, 0, depth, shift, kind, (ctypes.c_int32 * 9)(),
-                                 (ctypes.c_int32 * 5)(), (ctypes.c_float * 3)(), (ctypes.c_float * 3)(), s, d)
-
-    common = ((dict(h=5), -1, b"even"), (dict(w=3), -1, b"even"), (dict(h=0), -1, b""), (dict(w=0), -1, b""),
-              (dict(n=0), -1, b"batch"), (dict(n=65536), -1, b"batch"), (dict(s=None), -1, b"null"),
-              (dict(d=None), -1, b"null"), (dict(d=src), -1, b"dst must not be src"),
-              (dict(layout=2), -2, b"layout"), (dict(siting=-1), -2, b"siting"), (dict(siting=2), -2, b"siting"),
-              (dict(kind=3), -2, b"rgb_kind"), (dict(kind=-1), -2, b"rgb_kind"),
-              (dict(depth=8), -2, b"depth"), (dict(depth=12), -2, b"depth"), (dict(depth=16), -2, b"depth"),
-              (dict(shift=7), -2, b"shift"), (dict(shift=-1), -2, b"shift"), (dict(shift=16), -2, b"shift"),
-              (dict(h=32768, w=16384), -2, b"2^28"),
-              (dict(s=src + 1), -1, b"aligned"), (dict(d=dst + 1), -1, b"aligned"), (dict(s=src + 3, d=dst + 5), -1, b"aligned"))
-    per_fn = {
-        "isr_yuv420_to_rgb_16": ((dict(kind=TANH), -2, b"other direction"), (dict(kind=NORM, d=dst + 2), -1, b"4-byte"),
-                                 (dict(kind=NORM, s=src + 1), -1, b"2-byte")),
-        "isr_rgb_to_yuv420_16": ((dict(kind=NORM), -2, b"other direction"), (dict(kind=TANH, s=src + 2), -1, b"4-byte"),
-                                 (dict(kind=TANH, d=dst + 1), -1, b"2-byte")),
-    }
-    for name, own in per_fn.items():
-        fn = getattr(lib, name)
-        assert fn(None, None) == -1 and b"null descriptor" in lib.isr_last_error()
-        for kw, code, msg in common + own:
-            d = desc(**kw)
-            assert fn(ctypes.byref(d), None) == code, (name, kw, lib.isr_last_error())
-            assert msg in lib.isr_last_error(), (name, kw, lib.isr_last_error())

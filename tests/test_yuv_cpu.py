@@ -4,7 +4,7 @@ refusals, the builder as a stand-alone program under the address and undefined-b
 sanitizers, the integer restatement against the same filters and matrices in fp64 (the derived
 bound), greys, range end points and flat-colour round trips, the Y4M header and reader, the ffmpeg
 argv of the recorder and the reader, rs.py's flags, yuv.py's refusal of CPU tensors and the
-descriptor's layout against C."""
+descriptor's layout against C (what the two entry points refuse: tests/test_capi_refusals.py)."""
 import ctypes
 import itertools
 import subprocess
@@ -300,27 +300,6 @@ def test_format_and_cpu_tensors_refused():
         yuv.rgb_to_yuv420(torch.zeros((1, 3, 6, 10), dtype=torch.uint8))
     with pytest.raises(RuntimeError, match="HIP"):
         yuv.rgb_to_yuv420(np.zeros((1, 3, 6, 10), dtype=np.uint8))
-
-
-def test_entry_point_refusals():
-    """Descriptor validation happens before any launch: no GPU is touched by a refused call."""
-    lib = _lib.load()
-    buf = np.zeros(4096, dtype=np.uint8)
-    src, dst = buf.ctypes.data, buf.ctypes.data + 2048
-
-    def desc(n=1, h=4, w=4, layout=0, siting=0, s=src, d=dst):
-        return _lib.IsrYuvDesc(n, h, w, layout, siting, 0, (ctypes.c_int32 * 9)(), (ctypes.c_int32 * 5)(), s, d)
-
-    for fn in (lib.isr_yuv420_to_rgb_u8, lib.isr_rgb_to_yuv420_u8):
-        assert fn(None, None) == -1 and b"null descriptor" in lib.isr_last_error()
-        for kw, code, msg in ((dict(h=5), -1, b"even"), (dict(w=3), -1, b"even"), (dict(h=0), -1, b""),
-                              (dict(n=0), -1, b"batch"), (dict(n=65536), -1, b"batch"), (dict(s=None), -1, b"null"),
-                              (dict(d=None), -1, b"null"), (dict(d=src), -1, b"dst must not be src"),
-                              (dict(layout=2), -2, b"layout"), (dict(siting=-1), -2, b"siting"),
-                              (dict(h=32768, w=16384), -2, b"2^28")):
-            d = desc(**kw)
-            assert fn(ctypes.byref(d), None) == code, kw
-            assert msg in lib.isr_last_error(), (kw, lib.isr_last_error())
 
 
 PROBE = r"""
